@@ -15,14 +15,20 @@ results (b, GEBVs, μ̂) copied to pinned host memory.
 --loci 600000 --stream-chunk 75000`): the genotypes resident as int8 dosages (1 B per cell), each
 chunk of C loci standardised and added into G in place, the marker effects from the bytes.
 
-The C3 leg (`--c3-leg`, on by default whenever N > 1): after the headline, every rank
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, runs W untimed and K timed steps and prints the headline
+line. `--dump-outputs DIR` also writes the last timed step's results (B, y_pred, mu, msum) as DIR/<name>.npy; the
+inputs depend on the arguments alone, so two builds can be compared output for output. Every other leg runs only
+under `--full`: the exact-integer GRM beside the fp64 line, the C-ABI host path, the CPU baselines with the oracle
+parity, and the C3 leg.
+
+The C3 leg (`--full`; `--c3-leg`, on by default whenever N > 1): after the headline, every rank
 runs BASELINE.json configs[2] — n = 50 000, 600 000 loci SPLIT over the N ranks (75 000 per rank at N = 8, int8
 dosages resident, 75 000-locus fp64 chunks), the packed RCCL all-reduce of the partial GRMs, the distributed
 Cholesky (strip all-gathers) — 1 warm-up + 2 timed steps, reported under the line's "c3" key with the GRM and
 end-to-end fractions of N x the fp64 peak and every rank's GRM / all-reduce / solve / all-gather-wait times. The
 N = 1 headline is unchanged.
 
-Parity (rank 0, N = 1, when the oracle can run the same problem): the numpy restatement fits the
+Parity (`--full`; rank 0, N = 1, when the oracle can run the same problem): the numpy restatement fits the
 SAME genotypes and phenotypes the GPU step fitted; the line carries rel_err of y_pred, μ̂, b_hat and
 q equality.
 
@@ -62,8 +68,17 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="harness check without GPU work: rendezvous, barriers, max-over-ranks timing and the "
                          "rank-0 line around an empty step (value null); for CPU tests of the N-rank launcher")
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: the exact-integer GRM beside the fp64 line, the "
+                         "C-ABI host-path timings, the CPU baselines with the oracle parity, and the C3 leg (see "
+                         "--c3-leg); the --no-* options drop single legs. Without --full the run sets up, warms up, "
+                         "times --steps steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (B, y_pred, mu, msum of rank 0) "
+                         "as DIR/<name>.npy, float64; an array beyond its share of 64 MB is written as a fixed seeded "
+                         "sample of its elements")
     ap.add_argument("--individuals", type=int, default=5000)
     ap.add_argument("--loci", type=int, default=50000, help="loci per GPU")
     ap.add_argument("--nrhs", type=int, default=1)
@@ -81,7 +96,8 @@ def parse():
     ap.add_argument("--c3-leg", choices=("auto", "on", "off"), default="auto",
                     help="the C3 leg (BASELINE.json configs[2], the north star): after the headline, n = --c3-individuals "
                          "x --c3-loci loci SPLIT over the launched ranks (strong scaling), loci-streamed fp64 GRM, "
-                         "packed RCCL all-reduce, distributed Cholesky; auto = on when more than one rank runs")
+                         "packed RCCL all-reduce, distributed Cholesky; auto = on when more than one rank runs; "
+                         "runs under --full only")
     ap.add_argument("--c3-individuals", type=int, default=50000)
     ap.add_argument("--c3-loci", type=int, default=600000, help="loci in total (split over the ranks)")
     ap.add_argument("--c3-chunk", type=int, default=75000, help="loci per fp64 chunk of a rank's streamed shard")
@@ -95,7 +111,34 @@ def parse():
     ap.add_argument("--grm", choices=("fp64", "exact"), default="fp64",
                     help="fp64: the fp64-MFMA SYRK on standardised rows; exact: int8 dosages resident, the GRM "
                          "computed exactly by int8-MFMA digit GEMMs with int128 centring (csrc/grm_exact.hip)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.c3_leg == "on" and not args.full:
+        ap.error("--c3-leg on needs --full (a run without --full times the headline only)")
+    return args
+
+
+def c3_leg_on(args, world):
+    """The C3 leg runs under --full: when asked for (--c3-leg on), or by default with more than one rank."""
+    return args.full and (args.c3_leg == "on" or (args.c3_leg == "auto" and world > 1))
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+
+
+def dump_outputs(directory, out, seed=20240607):
+    """--dump-outputs: the arrays the last timed step returned (sharded_gblup_step's dict: B, y_pred, mu, msum) as
+    DIR/<name>.npy in float64. An array larger than its equal share of DUMP_LIMIT_BYTES is written as a sample of
+    its flattened elements at indices drawn once from a fixed seed (sorted, the same from run to run)."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (8 * max(len(out), 1)) - 16  # elements per array (16: room for the .npy header)
+    for name in sorted(out):
+        a = np.ascontiguousarray(np.asarray(out[name], dtype=np.float64))
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # BASELINE.json configs this bench can run (n, loci in total); the line names the one it ran
@@ -681,7 +724,7 @@ def launch_check(args, torch, dist, world, rank):
     else:
         ranks = [{"rank": 0, "pid": os.getpid()}]
     c3 = None
-    if args.c3_leg == "on" or (args.c3_leg == "auto" and world > 1):  # the record's shape around empty timings
+    if c3_leg_on(args, world):  # the record's shape around empty timings
         pr = [{"rank": r, "loci": c3_split(args.c3_loci, world, r)[1], "j0": c3_split(args.c3_loci, world, r)[0],
                "grm_ms": 0.0, "allreduce_ms": 0.0, "solve_ms": 0.0, "effects_ms": 0.0, "download_ms": 0.0,
                "allgather_blocked_ms": 0.0, "allgather_calls": 0, "allgather_bytes_received": 0,
@@ -887,11 +930,13 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, stage_ms)
     value = n * p_total / (ms_per_step / 1000.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # the exact-integer GRM path (§4.8) on the same genotypes and phenotypes, measured beside the fp64
-    # headline at N = 1: int8 dosages resident, the GRM exact up to each locus weight's fp64 rounding
+    # headline at N = 1 (--full): int8 dosages resident, the GRM exact up to each locus weight's fp64 rounding
     alt = None
-    if world == 1 and not exact and not args.stream_chunk and not args.no_exact:
+    if args.full and world == 1 and not exact and not args.stream_chunk and not args.no_exact:
         q_fp64 = int(st.q.item())
         ex = HipExactShardStages(n, p_local, nrhs=args.nrhs, lambda_=args.lam, device=dev)
         ex.generate(args.seed, j0)
@@ -924,9 +969,10 @@ def main():
     rec = headline_record(args, n, p_local, p_total, world, value, ms_per_step, syrk_ms, stage_ms, per_rank, exact,
                           grm_slices, digit_slices, dist) if rank == 0 else None
 
-    # the C3 leg (north star, BASELINE.json configs[2]): on by default whenever more than one rank runs. A watchdog
-    # bounds it: should a collective hang, rank 0 prints the headline line (its "c3" an error) and every rank exits
-    if args.c3_leg == "on" or (args.c3_leg == "auto" and world > 1):
+    # the C3 leg (north star, BASELINE.json configs[2]): under --full, on by default whenever more than one rank runs.
+    # A watchdog bounds it: should a collective hang, rank 0 prints the headline line (its "c3" an error) and every
+    # rank exits
+    if c3_leg_on(args, world):
         del st  # the headline shard's HBM back before the C3 shard is allocated
         dog = c3_watchdog(args, rank, rec)
 
@@ -954,6 +1000,11 @@ def main():
 
     if rank != 0:
         dist.destroy_process_group()
+        return
+    if not args.full:  # the headline only: the host-path, CPU-baseline and parity legs run under --full
+        print(json.dumps(rec), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
         return
     if world == 1 and not args.no_host_path and not args.stream_chunk and float(n) * p_local <= 2e9:
         rec["host_path"] = host_path(args, torch)

@@ -57,9 +57,9 @@ def test_gpus_must_match_launched_world_size():
 
 
 def test_c3_leg_record_at_two_ranks():
-    """--gpus 2 turns the C3 leg on (auto): the line carries the "c3" record with the loci split over the two
+    """--full --gpus 2 turns the C3 leg on (auto): the line carries the "c3" record with the loci split over the two
     ranks, the fractions' fields and one stage-time entry per rank (timings empty under --launch-check)."""
-    out = _run(["--gpus", "2", "--same-device", "--launch-check", "--steps", "1", "--warmup", "0"])
+    out = _run(["--full", "--gpus", "2", "--same-device", "--launch-check", "--steps", "1", "--warmup", "0"])
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     c3 = rec["c3"]

@@ -138,8 +138,8 @@ def test_bench_c3_leg_two_ranks_same_device():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--dist-backend", "gloo",
-           "--individuals", "2000", "--loci", "5000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--same-device", "--dist-backend",
+           "gloo", "--individuals", "2000", "--loci", "5000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
            "--no-exact", "--no-host-path", "--c3-leg", "on", "--c3-individuals", "20000", "--c3-loci", "60000",
            "--c3-chunk", "15000", "--c3-steps", "1", "--c3-warmup", "1"]
     env = dict(os.environ)
@@ -147,6 +147,8 @@ def test_bench_c3_leg_two_ranks_same_device():
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+    for leg in ("c3", "c3_exact_grm"):  # a leg that raised is reported in the line: show why (the ranks' stderr)
+        assert "error" not in rec[leg], rec[leg]["error"] + "\n" + out.stderr[-3000:]
     c3 = rec["c3"]
     print("\nC3 leg (reduced, 2 ranks on one GPU, gloo):", json.dumps(c3))
     assert c3["ranks"] == 2 and c3["n"] == 20000 and c3["p_total"] == 60000

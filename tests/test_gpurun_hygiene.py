@@ -49,12 +49,24 @@ def _ignored(rel, pats):
     return False
 
 
+def _tree_files():
+    """Every file beneath ROOT (relative paths), for a checkout without git metadata (an exported tree)."""
+    files = []
+    for base, dirs, names in os.walk(ROOT):
+        dirs[:] = [d for d in dirs if d not in (".git", "__pycache__", ".pytest_cache")]
+        files += [os.path.relpath(os.path.join(base, f), ROOT) for f in names]
+    return files
+
+
 def _travelling_files():
-    out = subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True, check=True).stdout
-    untracked = subprocess.run(["git", "ls-files", "--others", "--exclude-standard"], cwd=ROOT,
-                               capture_output=True, text=True, check=True).stdout
+    try:
+        out = subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+        untracked = subprocess.run(["git", "ls-files", "--others", "--exclude-standard"], cwd=ROOT,
+                                   capture_output=True, text=True, check=True).stdout
+        files = sorted(set(out.split()) | set(untracked.split()))
+    except (OSError, subprocess.CalledProcessError):  # no git, or not a work tree: scan what is on disk
+        files = sorted(_tree_files())
     pats = _ignore_patterns()
-    files = sorted(set(out.split()) | set(untracked.split()))
     return [f for f in files if (f.endswith(SCANNED_EXT) or os.path.basename(f) == "Makefile")
             and not _ignored(f, pats) and os.path.exists(os.path.join(ROOT, f))]
 

@@ -6,4 +6,4 @@ mkdir -p $O
 timeout -k 5 120 python -c "import torch; torch.zeros(1, device='cuda'); print('warm')" &&
 timeout -k 10 1000 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/gpu_suite.log 2>&1 &&
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1 &&
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err

@@ -13,7 +13,7 @@ mkdir -p $OUT
 STEPS=${STEPS:-5}
 WARM=${WARM:-2}
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-  python3 bench.py --steps $STEPS --warmup $WARM > $OUT/bench.json 2> $OUT/bench.err &&
+  python3 bench.py --full --steps $STEPS --warmup $WARM > $OUT/bench.json 2> $OUT/bench.err &&
 python3 tools/rocprof_stats.py $OUT/trace --warmup $WARM --steps $STEPS --step-start standardize_kernel --csv $OUT/kernel_stats_timed.csv > $OUT/kernel_stats_timed.txt &&
 python3 tools/rocprof_stats.py $OUT/trace --warmup $WARM --steps $STEPS --step-start xg_stats_kernel --csv $OUT/kernel_stats_timed_exact.csv > $OUT/kernel_stats_timed_exact.txt &&
 bash tools/profile_pmc.sh > $OUT/pmc.txt &&
