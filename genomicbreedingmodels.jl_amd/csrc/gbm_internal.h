@@ -21,6 +21,7 @@ inline int64_t gdim_of(int64_t n) { return npad_of(n) + kRhsRows; }
 
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+const std::string& last_error();  // the calling thread's message (gbm_last_error)
 
 // GBM_* tuning/test knobs (knobs.cpp): the environment is read once, at the first lookup; afterwards
 // values change only through gbm_debug_set. knob() returns the value (a pointer valid for the life of

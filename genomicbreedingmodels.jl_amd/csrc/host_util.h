@@ -1,5 +1,6 @@
-// Host-side helpers shared by the libgbm entry points (capi.cpp, session.cpp): RAII device
-// buffers and streams, device-list and phenotype validation. Not part of the ABI.
+// Host-side helpers shared by the libgbm entry points (capi.cpp, shard_grm.cpp and dist_solve.cpp
+// through fit_ctx.h; session.cpp): RAII device buffers and streams, device-list and phenotype
+// validation. Not part of the ABI.
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -51,7 +52,7 @@ inline std::atomic<int64_t>& alloc_counter() {
 }
 
 // When a device allocation runs out of memory, every registered trim callback frees the idle pooled
-// contexts of that device (capi.cpp: GBLUP fit contexts; gibbs.hip: BRR contexts, which also hold
+// contexts of that device (fit_ctx.h: GBLUP fit contexts; gibbs.hip: BRR contexts, which also hold
 // their captured graphs) and returns how many it freed; the allocation is then retried once.
 using TrimFn = int64_t (*)(int dev);
 struct OomTrim {

@@ -535,7 +535,7 @@ class HipShardStages:
 
 def chunk_schedule(p: int, chunk: int, halve_tail: bool = False):
     """Loci chunks [(j, pc), ...] of a streamed shard: chunks of ``chunk`` loci; with ``halve_tail`` the
-    last full piece cut into halving pieces (none below 512 loci). Mirrors csrc/capi.cpp chunk_schedule
+    last full piece cut into halving pieces (none below 512 loci). Mirrors csrc/shard_grm.cpp chunk_schedule
     (the C ABI halves only for copy-bound fp64 uploads at n <= 8192 or when GBM_HOST_CHUNK is set)."""
     cs, j = [], 0
     while p - j > chunk:
@@ -560,7 +560,7 @@ class HipStreamedShardStages(HipShardStages):
     the loci pass through one fp64 chunk buffer — each chunk standardised from the bytes and its GRM
     added into G in place (chunk GRMs summed in chunk order); the marker effects re-read the bytes with
     z rebuilt in registers. The same chunks and kernels as the C ABI's loci-streamed mode
-    (csrc/capi.cpp stream_grm_shard / stream_effects_shard), so the results are the same bits."""
+    (csrc/shard_grm.cpp stream_grm_shard / stream_effects_shard), so the results are the same bits."""
 
     def __init__(self, n: int, p_local: int, chunk: int, nrhs: int = 1, lambda_: float = 1.0, device: int = 0,
                  ploidy: int = 2, halve_tail: bool = False):

@@ -50,7 +50,7 @@ def test_same_device_shards_match_oracle(devices, n, p, t):
 ])
 def test_cabi_distributed_factorisation_bit_identical(gbm_env, devices, n, lims, tail):
     """gbm_gblup_fit with several device leaders factors V across them (solve_distributed in
-    capi.cpp: own-tile trailing updates, strip all-gathers, redundant tail). Rehearsed on one GPU
+    dist_solve.cpp: own-tile trailing updates, strip all-gathers, redundant tail). Rehearsed on one GPU
     with every shard its own leader (GBM_SHARD_LEADERS=each: copy all-reduce and copy all-gather
     in place of RCCL); bit-identical to the default path, where the shards' partial GRMs are summed
     on the device and one leader solves redundantly."""
@@ -220,7 +220,7 @@ def test_pipelined_host_upload_matches_oracle(gbm_env, chunk, carry):
     ([0, 0], "500", None), ([0, 0, 0], "700", None), ([0, 0], "500", "each"), ([0, 0], "0", None)])
 def test_multi_shard_fit_concurrent_equals_serial(gbm_env, devices, chunk, leaders):
     """The in-process multi-device fit drives every shard's upload, standardisation and partial GRM
-    from its own host thread (capi.cpp parallel_shards; VERDICT r02 Missing #1): shard k+1's upload
+    from its own host thread (fit_ctx.h parallel_shards; VERDICT r02 Missing #1): shard k+1's upload
     no longer waits for shard k's GRM. Same-device shards rehearse it on one GPU. Bit-identical to
     the one-after-the-other schedule (GBM_SHARD_THREADS=0) for the chunked host upload, the
     one-piece upload, both leader modes, the int8 entry and the GRM entries; matches the oracle."""

@@ -1,4 +1,4 @@
-"""Loci-streamed fits on the GPU (csrc/capi.cpp stream_grm_shard / stream_effects_shard): a shard whose
+"""Loci-streamed fits on the GPU (csrc/shard_grm.cpp stream_grm_shard / stream_effects_shard): a shard whose
 fp64 locus rows do not fit HBM keeps its genotypes as int8 dosages (or on the host, fp64 input) and
 passes the loci through one fp64 chunk buffer, each chunk's GRM added into G in place. That is how
 config C3 (n = 50 000 x p = 600 000, BASELINE configs[2]) runs on one MI355X
@@ -35,6 +35,11 @@ def data():
     return X, Y
 
 
+@pytest.fixture(scope="module")
+def ref(data):
+    return oracle.gblup_fit(*data, 1.0)
+
+
 def _fit_synth(gbm_env, stream, Y, devices=(0,), host_chunk=None):
     gbm_env.setenv("GBM_STREAM_CHUNK", str(stream))
     if host_chunk:
@@ -44,10 +49,9 @@ def _fit_synth(gbm_env, stream, Y, devices=(0,), host_chunk=None):
     return gbm.gblup_synthetic(SEED, N, P, Y, lambda_=1.0, devices=list(devices))
 
 
-def test_streamed_synthetic_matches_oracle_and_resident(gbm_env, data):
+def test_streamed_synthetic_matches_oracle_and_resident(gbm_env, data, ref):
     X, Y = data
     b, y, mu, q = _fit_synth(gbm_env, CHUNK, Y)
-    ref = oracle.gblup_fit(X, Y, 1.0)
     assert q == ref["q"]
     assert rel(y, ref["y_pred"]) < 1e-9 and rel(mu, ref["mu"]) < 1e-9 and rel(b, ref["b_hat"]) < 1e-6
     b0, y0, mu0, q0 = _fit_synth(gbm_env, 0, Y)
@@ -102,6 +106,32 @@ def test_streamed_single_range_tail_chunk(gbm_env, data):
     b, y, mu, q = _fit_synth(gbm_env, chunk, Y)
     b0, y0, mu0, q0 = _fit_synth(gbm_env, 0, Y)
     assert q == q0 and rel(y, y0) < 1e-12 and rel(b, b0) < 1e-10
+
+
+def test_single_range_tail_chunk_same_bits_streamed_pipelined_packed(gbm_env, data, ref):
+    """The chunk step's Gc branch (a chunk planning a single loci range) from all three chunked drivers on fp64
+    host X: chunk = P - 16 with GBM_HOST_CHUNK set gives the schedule (0, 4984), (4984, 16) in each (16 / 2 < 512:
+    no halving), so the loci-streamed fit, the pipelined fp64 upload and the host-packed pipeline sum the same
+    two chunk GRMs of the same standardised bits in the same order: the same result bits. The streamed fit is
+    also held to the oracle at this file's tolerances."""
+    X, Y = data
+    lib = gbm.load_library()
+    chunk = P - 16
+    assert lib.gbm_dev_grm_slices(N, 16) == 1 and lib.gbm_dev_grm_slices(N, chunk) > 1
+    gbm_env.setenv("GBM_HOST_CHUNK", str(chunk))
+    gbm_env.setenv("GBM_STREAM_CHUNK", str(chunk))
+    streamed = gbm.gblup_arrays(X, Y)
+    gbm_env.setenv("GBM_STREAM_CHUNK", "0")
+    gbm_env.setenv("GBM_HOST_PACK", "0")
+    pipelined = gbm.gblup_arrays(X, Y)
+    gbm_env.setenv("GBM_HOST_PACK", "1")
+    packed = gbm.gblup_arrays(X, Y)
+    for s, r, k in zip(streamed, pipelined, packed):  # b_hat, y_pred, mu, q
+        assert np.array_equal(np.asarray(s), np.asarray(r))
+        assert np.array_equal(np.asarray(s), np.asarray(k))
+    b, y, mu, q = streamed
+    assert q == ref["q"]
+    assert rel(y, ref["y_pred"]) < 1e-9 and rel(mu, ref["mu"]) < 1e-9 and rel(b, ref["b_hat"]) < 1e-6
 
 
 def test_streamed_two_shards_one_device(gbm_env, data):

@@ -4,7 +4,7 @@
 set -e
 cd "$(dirname "$0")/.."
 B=genomicbreedingmodels.jl_amd/csrc/build
-ALL="stats.hip grm.hip grm_exact.hip chol.hip chol_flow.hip effects.hip gibbs.hip capi.cpp session.cpp knobs.cpp hostpack.cpp"
+ALL="stats.hip grm.hip grm_exact.hip chol.hip chol_flow.hip effects.hip gibbs.hip capi.cpp shard_grm.cpp dist_solve.cpp session.cpp knobs.cpp hostpack.cpp"
 mkdir -p variants
 build() {  # name source flags...
   name=$1; src=$2; shift 2
