@@ -652,6 +652,136 @@ __global__ void __launch_bounds__(256) back_solve_kernel(const double* __restric
   }
 }
 
+// ---- whitening of locus rows against the finished factor: R <- R U⁻¹ (each row r becomes U⁻ᵀr) ----
+// What a finished gbm_dev_gblup_solve leaves behind (either factorisation path), and what is read here:
+//   · the off-diagonal 64x64 blocks U_mk (m < k) in G's upper part, rows 64m.., columns 64k..;
+//   · the factored diagonal blocks U_kk in Ld (npad x 64), their inverses in Linv (npad x 64, row-major
+//     upper, written by diag_inverse_kernel; identity in the padding blocks' padding rows);
+//   · the padding rows/columns [n, npad) of V are identity, so U is identity there and a row's padding
+//     columns stay what they were (0 when 0).
+// One workgroup owns a strip of WR = 64 locus rows and sweeps the column blocks k = 0 … nb − 1 alone:
+//   W_k = (R_k − Σ_{m<k} W_m U_mk) · U_kk⁻¹
+// in place (W_m overwrites R_m). No flags, no waits on other workgroups: strips are independent. The strip's
+// earlier blocks W_m are re-read from global memory (stored by all four waves; every store is waited for
+// and a workgroup barrier passed before any wave reads them). Eight waves (two per SIMD, so that one hides the
+// other's LDS and barrier waits) each accumulate a 32x16 part of the 64x64 block in fp64 MFMA accumulators; the W_m tile (pitch WPA, read as the A operand [row][k]) and the
+// U_mk tile (pitch PS, the B operand [k][col]) are staged through double-buffered LDS images (one barrier per
+// step), the global loads of steps m + 1 and m + 2 in flight during step m's MFMAs. Every output row is a function of its own input row only (MFMA rows do not mix,
+// the m and k orders are fixed), so a row's bits do not depend on the strip, chunk or launch it fell into.
+// Rows past `rows` (a ragged last strip) are loaded as zeros and never stored.
+constexpr int WPA = CNB + 4;  // pitch of the A-operand image: [row = lane & 15][k = lane >> 4] reads conflict-free
+__global__ void __launch_bounds__(512) whiten_rows_kernel(const double* __restrict__ G, int64_t ldg,
+                                                          const double* __restrict__ Linv, int64_t nb, double* R,
+                                                          int64_t ldr, int64_t rows) {
+  __shared__ __attribute__((aligned(16))) double As[2][CNB * WPA];  // double-buffered: one barrier per step
+  __shared__ __attribute__((aligned(16))) double Bs[2][CNB * PS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3, fr = lane >> 4, fc = lane & 15;  // the wave's 32 x 16 part of the block
+  const int64_t r0 = (int64_t)blockIdx.x * CNB;
+  // staging: 16 bytes at column lcol of rows lrow + 16 e (e < 4): a wave instruction covers two whole 512-byte rows
+  const int lrow = tid >> 5, lcol = 2 * (tid & 31);
+  const int cw = wn * 16 + fc;  // this lane's column of the block
+  typedef double d8 __attribute__((ext_vector_type(8)));
+  for (int64_t k = 0; k < nb; k++) {
+    d4 acc[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int64_t row = r0 + wm * 32 + m * 16 + fr + 4 * r;
+        acc[m][r] = row < rows ? R[row * ldr + k * CNB + cw] : 0.0;
+      }
+    // two register sets: the loads of steps m + 1 and m + 2 are in flight during step m's MFMAs (with one step
+    // in flight the sweep was bound by the latency of its own loads); step s uses set s & 1
+    d8 va0, vb0, va1, vb1;
+    auto load_step = [&](int64_t m, d8& va, d8& vb) {
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const int64_t row = r0 + lrow + 16 * e;
+        double2 x = make_double2(0.0, 0.0);
+        if (row < rows) x = *reinterpret_cast<const double2*>(R + row * ldr + m * CNB + lcol);
+        const double2 y = *reinterpret_cast<const double2*>(G + (m * CNB + lrow + 16 * e) * ldg + k * CNB + lcol);
+        va[2 * e] = x.x;
+        va[2 * e + 1] = x.y;
+        vb[2 * e] = y.x;
+        vb[2 * e + 1] = y.y;
+      }
+    };
+    auto stage = [&](int buf, const d8& va, const d8& vb) {
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        *reinterpret_cast<double2*>(&As[buf][(lrow + 16 * e) * WPA + lcol]) = make_double2(va[2 * e], va[2 * e + 1]);
+        *reinterpret_cast<double2*>(&Bs[buf][(lrow + 16 * e) * PS + lcol]) = make_double2(vb[2 * e], vb[2 * e + 1]);
+      }
+    };
+    // step m from image m & 1 (= buf); then step m + 1's set -> the other image (its last readers, step m − 1,
+    // passed the barrier that ended that step) and step m + 3's loads into the freed set
+    auto step = [&](int64_t m, int buf, d8& na, d8& nb_) {
+      const double* Am = As[buf];
+      const double* Bm = Bs[buf];
+#pragma unroll
+      for (int ks = 0; ks < 16; ks++) {
+        const double bf = Bm[(ks * 4 + fr) * PS + cw];
+#pragma unroll
+        for (int mm = 0; mm < 2; mm++) {
+          const double af = -Am[(wm * 32 + mm * 16 + fc) * WPA + ks * 4 + fr];
+          acc[mm] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[mm], 0, 0, 0);
+        }
+      }
+      if (m + 1 < k) {
+        stage(buf ^ 1, na, nb_);
+        if (m + 3 < k) load_step(m + 3, na, nb_);
+      }
+      __syncthreads();  // step m + 1's images are complete; every wave is done with step m's
+    };
+    if (k > 0) {
+      load_step(0, va0, vb0);
+      if (k > 1) load_step(1, va1, vb1);
+      stage(0, va0, vb0);
+      if (k > 2) load_step(2, va0, vb0);
+      __syncthreads();
+    }
+    for (int64_t m = 0; m < k; m += 2) {
+      step(m, 0, va1, vb1);
+      if (m + 1 < k) step(m + 1, 1, va0, vb0);
+    }
+    // W_k = acc · U_kk⁻¹: acc -> the A image, U_kk⁻¹ (Linv, [k][col]) -> the B image
+    // (the barrier that ended the last step freed the images)
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) As[0][(wm * 32 + m * 16 + fr + 4 * r) * WPA + cw] = acc[m][r];
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+      *reinterpret_cast<double2*>(&Bs[0][(lrow + 16 * e) * PS + lcol]) =
+          *reinterpret_cast<const double2*>(Linv + (k * CNB + lrow + 16 * e) * CNB + lcol);
+    __syncthreads();
+    d4 out[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) out[m] = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < 16; ks++) {
+      const double bf = Bs[0][(ks * 4 + fr) * PS + cw];
+#pragma unroll
+      for (int mm = 0; mm < 2; mm++) {
+        const double af = As[0][(wm * 32 + mm * 16 + fc) * WPA + ks * 4 + fr];
+        out[mm] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, out[mm], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int64_t row = r0 + wm * 32 + m * 16 + fr + 4 * r;
+        if (row < rows) R[row * ldr + k * CNB + cw] = out[m][r];
+      }
+    // W_k is in memory (this wave's stores are complete) before any wave of the workgroup re-reads it, and
+    // every wave is done with the images
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+  }
+}
+
 // ---- GEBV = μ̂ + (y − μ̂) − λ a ------------------------------------------------------------
 __global__ void __launch_bounds__(256) gebv_kernel(const double* __restrict__ Y, int64_t ldy, int64_t n,
                                                    const double* __restrict__ A, double* __restrict__ gebv,
@@ -1107,6 +1237,22 @@ extern "C" int gbm_dev_gblup_terms(const double* G, int64_t ldg, int64_t n, int6
     return fail(GBM_E_ARG, "gbm_dev_gblup_terms: bad arguments");
   gblup_terms_kernel<<<1, 256, 0, (hipStream_t)stream>>>(G, ldg, npad_of(n), nrhs, (const double*)workspace,
                                                          terms);
+  GBM_LAUNCH_CHECK();
+  return GBM_OK;
+}
+
+extern "C" int gbm_dev_whiten_rows(const double* G, int64_t ldg, int64_t n, const void* solve_workspace, double* R,
+                                   int64_t ldr, int64_t rows, void* stream) {
+  const int64_t npad = npad_of(n);
+  if (!G || !solve_workspace || !R || n < 1 || rows < 0 || ldg < gdim_of(n) || (ldg & 1) || ((uintptr_t)G & 15) ||
+      ldr < npad || (ldr & 1) || ((uintptr_t)R & 15) || ((uintptr_t)solve_workspace & 15))
+    return fail(GBM_E_ARG, "gbm_dev_whiten_rows: bad arguments (G, R 16-byte aligned, even ldg >= gdim(n), even ldr >= "
+                           "npad(n), rows >= 0, the workspace of the finished gbm_dev_gblup_solve)");
+  if (rows == 0) return GBM_OK;
+  const int64_t strips = (rows + CNB - 1) / CNB;
+  if (strips > 0x7fffffff) return fail(GBM_E_ARG, "gbm_dev_whiten_rows: too many rows for one launch");
+  const SolveWs w = solve_ws(const_cast<void*>(solve_workspace), npad);
+  whiten_rows_kernel<<<(unsigned)strips, 512, 0, (hipStream_t)stream>>>(G, ldg, w.Linv, npad / NB, R, ldr, rows);
   GBM_LAUNCH_CHECK();
   return GBM_OK;
 }

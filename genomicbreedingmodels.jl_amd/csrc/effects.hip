@@ -263,6 +263,121 @@ int launch_weighted_sum(const double* mean, const double* B, int64_t ldb, int64_
   return GBM_OK;
 }
 
+// ---- GWAS statistics of (whitened) locus rows: one pass over a chunk -------------------------------
+// Row w_j (n individuals), K covariate rows c_0 … c_{K−1} (c_0 the intercept; whitened like w_j in the mixed
+// model) and the response row ỹ: d = w·w, v = w·ỹ, g_c = w·c_c, then the Schur complement of the bordered
+// normal equations (reference src/gwas.jl:591-599 and 241-245, X = [C, x_j]):
+//   s = d − gᵀA⁻¹g,  num = v − gᵀ(A⁻¹u),  b = num/s,  z = zscale · num/√s     (A = CᵀC, u = Cᵀỹ, host fp64).
+// keep[j] == 0 or s <= 1e-12 d (the locus lies in the covariates' span): b = z = 0 and the locus is not counted.
+// One wave per row, as marker_effects_kernel: lane l takes individuals 4l + 256k in order (fma chains), then an
+// xor-shuffle tree — a fixed order, so the statistics are bit-reproducible and independent of the chunking.
+template <int K>
+__global__ void __launch_bounds__(256) gwas_stats_kernel(const double* __restrict__ W, int64_t ldw, int64_t rows,
+                                                         int64_t n, const double* __restrict__ Cw, int64_t ldcw,
+                                                         const double* __restrict__ yw, GwasCoef co,
+                                                         const int32_t* __restrict__ keep, double* __restrict__ z,
+                                                         double* __restrict__ b, double* __restrict__ s_out,
+                                                         unsigned long long* __restrict__ tested) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave_g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  for (int64_t j = wave_g; j < rows; j += nwaves) {
+    const bool kp = keep[j] != 0;
+    double acc[K + 2];
+#pragma unroll
+    for (int c = 0; c < K + 2; c++) acc[c] = 0.0;
+    if (kp) {
+      const double* wr = W + j * ldw;
+      for (int64_t i = (int64_t)lane * 4; i < n; i += 256) {
+        const bool whole = i + 4 <= n;
+        auto load4 = [&](const double* src, double (&o)[4]) {
+          if (whole) {
+            const double2 v0 = *reinterpret_cast<const double2*>(src + i);
+            const double2 v1 = *reinterpret_cast<const double2*>(src + i + 2);
+            o[0] = v0.x;
+            o[1] = v0.y;
+            o[2] = v1.x;
+            o[3] = v1.y;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[e] = i + e < n ? src[i + e] : 0.0;
+          }
+        };
+        double wv[4], xv[4];
+        load4(wr, wv);
+#pragma unroll
+        for (int e = 0; e < 4; e++) acc[0] = __builtin_fma(wv[e], wv[e], acc[0]);
+        load4(yw, xv);
+#pragma unroll
+        for (int e = 0; e < 4; e++) acc[1] = __builtin_fma(wv[e], xv[e], acc[1]);
+#pragma unroll
+        for (int c = 0; c < K; c++) {
+          load4(Cw + c * ldcw, xv);
+#pragma unroll
+          for (int e = 0; e < 4; e++) acc[2 + c] = __builtin_fma(wv[e], xv[e], acc[2 + c]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < K + 2; c++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[c] += __shfl_xor(acc[c], off, 64);
+    }
+    if (lane == 0) {
+      double zj = 0.0, bj = 0.0, sj = 0.0;
+      if (kp) {
+        const double d = acc[0];
+        double gAg = 0.0, gAu = 0.0;
+#pragma unroll
+        for (int a = 0; a < K; a++) {
+          double t = 0.0;
+#pragma unroll
+          for (int c = 0; c < K; c++) t = __builtin_fma(co.Ainv[a * 8 + c], acc[2 + c], t);
+          gAg = __builtin_fma(acc[2 + a], t, gAg);
+          gAu = __builtin_fma(acc[2 + a], co.Au[a], gAu);
+        }
+        sj = d - gAg;
+        if (sj > 1e-12 * d) {
+          const double num = acc[1] - gAu;
+          bj = num / sj;
+          zj = co.zscale * (num / sqrt(sj));
+          atomicAdd(tested, 1ULL);  // an integer count: the order of the additions does not matter
+        }
+      }
+      z[j] = zj;
+      if (b) b[j] = bj;
+      if (s_out) s_out[j] = sj;
+    }
+  }
+}
+
+template <int K>
+static void gwas_stats_launch(unsigned blocks, const double* W, int64_t ldw, int64_t rows, int64_t n, const double* Cw,
+                              int64_t ldcw, const double* yw, const GwasCoef& co, const int32_t* keep, double* z,
+                              double* b, double* s_out, unsigned long long* tested, hipStream_t s) {
+  gwas_stats_kernel<K><<<blocks, 256, 0, s>>>(W, ldw, rows, n, Cw, ldcw, yw, co, keep, z, b, s_out, tested);
+}
+
+int launch_gwas_stats(const double* W, int64_t ldw, int64_t rows, int64_t n, const double* Cw, int64_t ldcw,
+                      const double* yw, const GwasCoef& co, const int32_t* keep, double* z, double* b, double* s_out,
+                      unsigned long long* tested, hipStream_t s) {
+  if (rows < 1) return GBM_OK;
+  if (co.kcov < 1 || co.kcov > 8 || (ldw & 1) || (ldcw & 1) || ((uintptr_t)W & 15) || ((uintptr_t)Cw & 15) ||
+      ((uintptr_t)yw & 15))
+    return fail(GBM_E_ARG, "gwas statistics: 1 to 8 covariate rows, even strides, 16-byte aligned rows");
+  const unsigned blocks = (unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
+  switch (co.kcov) {
+#define GBM_GWAS_CASE(K) \
+  case K:                \
+    gwas_stats_launch<K>(blocks, W, ldw, rows, n, Cw, ldcw, yw, co, keep, z, b, s_out, tested, s); \
+    break;
+    GBM_GWAS_CASE(1) GBM_GWAS_CASE(2) GBM_GWAS_CASE(3) GBM_GWAS_CASE(4) GBM_GWAS_CASE(5) GBM_GWAS_CASE(6)
+    GBM_GWAS_CASE(7) GBM_GWAS_CASE(8)
+#undef GBM_GWAS_CASE
+  }
+  GBM_LAUNCH_CHECK();
+  return GBM_OK;
+}
+
 int64_t predict_chunks(int64_t n, int64_t p) {
   const int64_t col_blocks = (n + 255) / 256;
   int64_t c = (2048 + col_blocks - 1) / col_blocks;

@@ -110,6 +110,17 @@ class ChunkPacker {
 int resolve_grm_mode(int grm_mode);
 int launch_weighted_sum(const double* mean, const double* B, int64_t ldb, int64_t p, int64_t nrhs, double* msum,
                         hipStream_t s);
+// GWAS statistics of locus rows (effects.hip): A⁻¹ (row-major, pitch 8) and A⁻¹u of the kcov covariate rows
+// (1 ≤ kcov ≤ 8, the intercept first), zscale on z; see gwas_stats_kernel
+struct GwasCoef {
+  double Ainv[64];
+  double Au[8];
+  double zscale;
+  int32_t kcov;
+};
+int launch_gwas_stats(const double* W, int64_t ldw, int64_t rows, int64_t n, const double* Cw, int64_t ldcw,
+                      const double* yw, const GwasCoef& co, const int32_t* keep, double* z, double* b, double* s_out,
+                      unsigned long long* tested, hipStream_t s);
 int launch_center_columns(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz, double* mean,
                           double* sd, int32_t* keep, int64_t* q_dev, hipStream_t s);
 

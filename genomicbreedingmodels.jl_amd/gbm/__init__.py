@@ -11,6 +11,7 @@ from .prediction import LINEAR_MODELS, extractxyetc, predict
 from .types import Fit, Genomes, Phenomes
 from .arrays import colstats, grm, grm_ploidy_aware, infer_ploidy
 from .session import GenotypeSession
+from .gwas import gwasols, gwasreml
 from .bayes import bayesian, brr_arrays
 from .cv import CV, cvbulk, cvbulk_setup, cvmultithread, fold_assignments, validate
 
@@ -18,5 +19,5 @@ __all__ = [
     "ArgumentError", "GBMError", "device_count", "load_library",
     "gblup", "gblup_arrays", "gblup_dosage", "gblup_reml_arrays", "gblup_synthetic", "ridge", "ridge_path_cv", "ridge_select", "glmnet_folds", "metrics", "pearsonscorrelation", "r2", "heritabilitynarrow_sense",
     "LINEAR_MODELS", "extractxyetc", "predict", "Fit", "Genomes", "Phenomes", "colstats", "grm", "grm_ploidy_aware", "infer_ploidy",
-    "GenotypeSession", "bayesian", "brr_arrays", "CV", "cvbulk", "cvbulk_setup", "cvmultithread", "fold_assignments", "validate",
+    "GenotypeSession", "gwasreml", "gwasols", "bayesian", "brr_arrays", "CV", "cvbulk", "cvbulk_setup", "cvmultithread", "fold_assignments", "validate",
 ]

@@ -46,6 +46,7 @@ EXPORTS = (
     "gbm_gblup_fit_ex", "gbm_gblup_fit_reml_ex", "gbm_gblup_fit_dosage_i8_ex", "gbm_gblup_fit_synthetic_ex",
     "gbm_session_set_grm_mode", "gbm_session_grm_used", "gbm_debug_rccl_calls", "gbm_debug_xg_choose", "gbm_debug_chol_flow_order",
     "gbm_debug_chol_flow_order_check", "gbm_debug_chol_flow_order_size", "gbm_dev_grm_exact_status", "gbm_debug_set",
+    "gbm_dev_whiten_rows", "gbm_session_gwas",
 )
 
 GBM_GRM_DEFAULT, GBM_GRM_FP64, GBM_GRM_EXACT, GBM_GRM_AUTO, GBM_GRM_DROPIN = -1, 0, 1, 2, 3
@@ -236,6 +237,10 @@ def _declare(lib):
     lib.gbm_debug_chol_flow_order_check.argtypes = [I32, P, I64]
     lib.gbm_dev_grm_exact_status.restype = I32
     lib.gbm_dev_grm_exact_status.argtypes = [P, I64, I64, P]
+    lib.gbm_dev_whiten_rows.restype = I32
+    lib.gbm_dev_whiten_rows.argtypes = [P, I64, I64, P, P, I64, I64, P]
+    lib.gbm_session_gwas.restype = I32
+    lib.gbm_session_gwas.argtypes = [P, P, I64, P, P, I64, I64, I32, D, D, P, P, P, P]
     lib.gbm_debug_set.restype = I32
     lib.gbm_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     return lib

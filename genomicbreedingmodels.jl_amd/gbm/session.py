@@ -155,6 +155,48 @@ class GenotypeSession:
         _lib.check(rc, "gbm_session_reml")
         return {"lambda": float(v[0]), "sigma2_e": float(v[1]), "sigma2_u": float(v[2]), "objective": float(v[3])}
 
+    def gwas(self, idx, y, covariates=None, model: str = "mlm", sigma2=None) -> dict:
+        """GWAS scan over all p loci on rows ``idx`` (gbm_session_gwas; reference gwasreml / gwasols,
+        src/gwas.jl:591-599, 241-245). ``covariates``: (n_train,) or (n_train, kc <= 7) beside the intercept.
+        ``model``: "mlm" (V = σ²_u ZZᵀ/q + σ²_e I on the cached GRM factor) or "ols" (V = I). ``sigma2``:
+        (σ²_e, σ²_u) for "mlm", or None to estimate them once by the null-model REML of :meth:`reml`.
+        Returns dict(z (p,), b (p,), sigma2_e, sigma2_u, tested); untested loci (not polymorphic in the rows, or in
+        the covariates' span) have z = b = 0; sigma2_e/sigma2_u are None for "ols"."""
+        idx = _idx(idx)
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+        if y.shape != (idx.size,):
+            raise ArgumentError("y must have one value per training index")
+        try:
+            m = {"mlm": 0, "ols": 1}[model]
+        except (KeyError, TypeError):
+            raise ArgumentError(f"model must be 'mlm' or 'ols', got {model!r}") from None
+        if covariates is None:
+            C, kc = None, 0
+        else:
+            C = np.asarray(covariates, dtype=np.float64)
+            if C.ndim == 1:
+                C = C[:, None]
+            if C.ndim != 2 or C.shape[0] != idx.size:
+                raise ArgumentError("covariates must have one row per training index")
+            C = np.asfortranarray(C)
+            kc = C.shape[1]
+        if sigma2 is None:
+            s2e = s2u = float("nan")
+        else:
+            s2e, s2u = (float(v) for v in sigma2)
+            if m == 0 and (np.isnan(s2e) or np.isnan(s2u)):
+                raise ArgumentError("sigma2 must be a pair of positive numbers (None: estimate by REML)")
+        z = np.zeros(self.p)
+        b = np.zeros(self.p)
+        used = np.zeros(2)
+        tested = np.zeros(1, dtype=np.int64)
+        rc = self.lib.gbm_session_gwas(self._h, _lib.ptr(idx), idx.size, _lib.ptr(y), _lib.ptr(C) if kc else None,
+                                       idx.size, kc, m, s2e, s2u, _lib.ptr(z), _lib.ptr(b), _lib.ptr(used),
+                                       _lib.ptr(tested))
+        _lib.check(rc, "gbm_session_gwas")
+        return {"z": z, "b": b, "sigma2_e": None if m else float(used[0]), "sigma2_u": None if m else float(used[1]),
+                "tested": int(tested[0])}
+
     def ridge_lambda_max(self, idx, y) -> float:
         """glmnet's first λ for alpha = 0 on rows ``idx`` (standardize = false)."""
         idx = _idx(idx)

@@ -122,3 +122,73 @@ function gblup(;
     end
     fit
 end
+
+# ---- GWAS scans on the GPU (gbm_session_gwas; untested here like the rest of this file: no Julia in the
+# build container; the Python mirror gbm/gwas.py drives the same ccall) -------------------------------------
+# Both build the Fit with the reference's own gwasprep (src/gwas.jl:77-142) and replace the per-marker loop.
+# Differences from the reference loops, stated in include/gbm.h: the variance components are estimated once
+# under the null model (not per marker), K = ZZᵀ/q (not the column-standardised GRM), and the mixed model
+# runs on that simple GRM only (GRM_type = "ploidy-aware" is refused by gwasreml_gpu).
+function gbm_gwas_scan(G::Matrix{Float64}, y::Vector{Float64}, C::Matrix{Float64}, model::Integer; device::Integer = 0)
+    n, p = size(G)
+    kc = size(C, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    gbm_check(ccall((:gbm_session_create, LIBGBM), Cint,
+                    (Ptr{Float64}, Int64, Int64, Int64, Cint, Ptr{Ptr{Cvoid}}), G, n, p, n, device, h),
+              "gwas (session)")
+    z = zeros(p)
+    b = zeros(p)
+    σ2 = zeros(2)
+    tested = zeros(Int64, 1)
+    idx = collect(Int64, 0:(n-1))
+    try
+        gbm_check(ccall((:gbm_session_gwas, LIBGBM), Cint,
+                        (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Cint, Float64, Float64,
+                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                        h[], idx, n, y, kc > 0 ? C : Ptr{Float64}(C_NULL), n, kc, model, NaN, NaN, z, b, σ2, tested),
+                  "gwas")
+    finally
+        ccall((:gbm_session_destroy, LIBGBM), Cvoid, (Ptr{Cvoid},), h[])
+    end
+    (z = z, b = b, σ2_e = σ2[1], σ2_u = σ2[2], tested = tested[1])
+end
+
+"""
+    gwasreml_gpu(; genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, GRM_type="simple", verbose=false)::Fit
+
+`gwasreml` (src/gwas.jl:485-620) with the marker loop on the GPU: one null-model REML, one Cholesky, then
+z_j for every locus from rows whitened against that factor.
+"""
+function gwasreml_gpu(; genomes::Genomes, phenomes::Phenomes, idx_entries = nothing, idx_loci_alleles = nothing,
+                      idx_trait::Int64 = 1, GRM_type::String = "simple", verbose::Bool = false)::Fit
+    GRM_type == "simple" || throw(ArgumentError("gwasreml_gpu runs on the simple GRM (ZZᵀ/q) only"))
+    G, y, _, fit = gwasprep(genomes = genomes, phenomes = phenomes, idx_entries = idx_entries,
+                            idx_loci_alleles = idx_loci_alleles, idx_trait = idx_trait, GRM_type = GRM_type,
+                            standardise = true, verbose = false)
+    r = gbm_gwas_scan(G, y, zeros(size(G, 1), 0), 0)
+    fit.model = "GWAS_REML"
+    fit.b_hat = r.z   # gwasprep already dropped the loci without variance: every column of G is kept
+    verbose && println("gwasreml_gpu: tested=$(r.tested) σ²_e=$(r.σ2_e) σ²_u=$(r.σ2_u)")
+    checkdims(fit) || throw(ErrorException("Error performing GWAS via REML on the GPU."))
+    fit
+end
+
+"""
+    gwasols_gpu(; genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, GRM_type="simple", verbose=false)::Fit
+
+`gwasols` (src/gwas.jl:146-260) with the marker loop on the GPU; PC1 of the (standardised) GRM is computed on the
+host exactly as the reference does (src/gwas.jl:234).
+"""
+function gwasols_gpu(; genomes::Genomes, phenomes::Phenomes, idx_entries = nothing, idx_loci_alleles = nothing,
+                     idx_trait::Int64 = 1, GRM_type::String = "simple", verbose::Bool = false)::Fit
+    G, y, GRM, fit = gwasprep(genomes = genomes, phenomes = phenomes, idx_entries = idx_entries,
+                              idx_loci_alleles = idx_loci_alleles, idx_trait = idx_trait, GRM_type = GRM_type,
+                              standardise = true, verbose = false)
+    E = MultivariateStats.fit(PCA, GRM; maxoutdim = 1)
+    r = gbm_gwas_scan(G, y, reshape(E.proj[:, 1], :, 1), 1)
+    fit.model = "GWAS_OLS"
+    fit.b_hat = r.z
+    verbose && println("gwasols_gpu: tested=$(r.tested)")
+    checkdims(fit) || throw(ErrorException("Error performing GWAS via OLS on the GPU."))
+    fit
+end

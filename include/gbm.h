@@ -395,6 +395,15 @@ int gbm_dev_chol_finish(double* G, int64_t ldg, int64_t n, const double* Y, int6
 int gbm_dev_gblup_terms(const double* G, int64_t ldg, int64_t n, int64_t nrhs, const void* workspace,
                         double* terms, void* stream);
 
+/* Whitening of locus rows against the factor a finished gbm_dev_gblup_solve left behind (same G, n and
+ * workspace; V = G/q + λI = UᵀU): every row r of R (rows x ldr row-major, individuals contiguous like Zt,
+ * ldr >= gbm_dev_npad(n) even, 16-byte aligned) becomes r·U⁻¹ = U⁻ᵀr, in place. It reads the off-diagonal
+ * 64x64 blocks of U in G's upper part and the inverses of the diagonal blocks in the workspace, on fp64 MFMA;
+ * one workgroup per strip of 64 rows, strips independent. A row's result depends on that row alone (not on
+ * rows, the strip or the launch it fell into); the padding columns [n, npad) stay 0 when they are 0. */
+int gbm_dev_whiten_rows(const double* G, int64_t ldg, int64_t n, const void* solve_workspace, double* R,
+                        int64_t ldr, int64_t rows, void* stream);
+
 /*
  * Marker effects on the standardised locus rows: B[t, j] = (Zt_j · a_t)/(q·sd_j) for kept
  * loci, 0 otherwise (B nrhs x ldb row-major), and msum[t] = Σ_j mean_j B[t, j] over this
@@ -487,6 +496,29 @@ int gbm_session_ridge_lambda_max(gbm_session* s, const int64_t* idx, int64_t n_t
                                  double* lambda_max);
 /* GRM builds and cache hits so far. */
 int gbm_session_stats(gbm_session* s, int64_t* grm_builds, int64_t* grm_hits);
+/* GWAS scan over all p loci on the rows idx[0..n_train) (reference gwasreml / gwasols, src/gwas.jl). For the
+ * standardised locus column x_j (the session's cached Z) and X = [1, C, x_j]:
+ *   model 0 (mixed model): V = σ²_u·ZZᵀ/q + σ²_e·I, z_j = b[end]/sqrt(inv(XᵀV⁻¹X)[end]) (src/gwas.jl:591-599),
+ *     computed as a Schur complement on rows whitened against the cached GRM's Cholesky factor
+ *     (gbm_dev_whiten_rows, one bordered solve per call); b_j = b[end];
+ *   model 1 (OLS): V = I, z_j = b[end]/sqrt(inv(XᵀX)[end]) (src/gwas.jl:241-245; like the reference, no
+ *     residual variance enters).
+ * y (n_train) is standardised inside as gwasprep does (src/gwas.jl:128). C: extra covariates, column-major
+ * n_train x kc (ldc >= n_train), 0 <= kc <= 7; the intercept is always in the model. sigma2_e, sigma2_u (model 0):
+ * both > 0 = used as given; either NaN = estimated ONCE by the null-model REML of gbm_session_reml (intercept
+ * only). z_out, b_out (p each; b_out may be NULL); sigma2_out (2, may be NULL): the (σ²_e, σ²_u) used (NaN for
+ * model 1); tested_out (may be NULL): the loci tested. Loci that are not polymorphic in the training rows, or that
+ * lie in the span of the covariates (Schur complement <= 1e-12 x_jᵀV⁻¹x_j), get z = b = 0 and are not counted.
+ * Deliberate differences from the reference: (1) the variance components are estimated once under the null
+ * model (the usual P3D/EMMAX approximation), where the reference re-runs LBFGS for every marker; (2) the
+ * relationship matrix is K = ZZᵀ/q as in gbm_session_reml_objective, where the reference column-standardises K
+ * (which makes it non-symmetric); (3) the mixed model uses this simple GRM only (no ploidy-aware variant).
+ * The cached Z and GRM are not written: a later fit on the same idx is a cache hit with unchanged bits.
+ * GBM_GWAS_CHUNK (loci) overrides the chunk of rows whitened at a time (default: one 64-row strip per compute
+ * unit, balanced over the chunks; the chunk buffer stays under 768 MB). */
+int gbm_session_gwas(gbm_session* s, const int64_t* idx, int64_t n_train, const double* y, const double* C,
+                     int64_t ldc, int64_t kc, int model, double sigma2_e, double sigma2_u, double* z_out,
+                     double* b_out, double* sigma2_out, int64_t* tested_out);
 
 /*
  * ---- Bayesian ridge regression (BGLR model "BRR") by Gibbs sampling -------------------------
