@@ -20,7 +20,9 @@
 // GBM_GRM_PERSIST=0 (hardware-dispatched workgroups), GBM_GRM_EDGE=0 (no ragged-edge kernel),
 // GBM_GRM_EDGE_CONCURRENT=0 (edge kernel after the tiles), GBM_GRM_SPLIT=w0,w1,... (relative
 // loci-range sizes instead of the planner's), GBM_GRM_FUSED=1 (the slab reduce inside the persistent tile
-// kernel; same bits, opt-in: DESIGN.md §7, round 6).
+// kernel; same bits, opt-in: DESIGN.md §7, round 6), GBM_GRM_DIAG=0 (whole diagonal tiles in the quadrant
+// form instead of their 36 upper 16x16 blocks; same bits), GBM_GRM_DIAG_COST (the planner's cost of a
+// diagonal unit).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -151,6 +153,104 @@ __device__ __forceinline__ void tile_pass(const double* __restrict__ U, int64_t 
   __syncthreads();
 }
 
+// Diagonal GRM tile, upper 16x16 blocks only. G is upper-stored, so of a diagonal
+// tile's 8 x 8 grid of 16x16 MFMA blocks only the 36 blocks (I, J) with J >= I are needed. Wave W owns
+// block rows I = W (J = W..7) and I = 7 − W (J = 7−W..7): 9 blocks per wave, acc[0 .. 7−W] the first
+// row's and acc[8−W .. 8] the second's. The operand of block row or column X is
+// A[kr][16 X + (lane & 15)]: row and column operand of one X are the same value, so a wave reads
+// X = W..7 once per k-step. W is a template parameter: every register index is a constant.
+template <int W>
+__device__ __forceinline__ void diag_step(const double* __restrict__ Ak, d4 (&acc)[9]) {
+  double x[8];
+#pragma unroll
+  for (int X = W; X < 8; X++) x[X] = Ak[16 * X];
+  __builtin_amdgcn_s_setprio(1);  // (as in tile_pass)
+#pragma unroll
+  for (int J = W; J < 8; J++) acc[J - W] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[W], x[J], acc[J - W], 0, 0, 0);
+#pragma unroll
+  for (int J = 7 - W; J < 8; J++)
+    acc[1 + J] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[7 - W], x[J], acc[1 + J], 0, 0, 0);  // 8−W + J−(7−W)
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// Block (I, J) holds tile element (16 I + (lane >> 4) + 4 reg, 16 J + (lane & 15)); `out` points at
+// element (lane >> 4, lane & 15) of the tile (pitch ld). The 8 blocks I = J are stored whole; the
+// blocks below them are not written (as undefined as a diagonal tile's lower-left quadrant).
+template <int W>
+__device__ __forceinline__ void diag_store(double* __restrict__ out, int64_t ld, const d4 (&acc)[9]) {
+  // row offsets as scalar values added to the pointer (as constant multiples of ld folded into the
+  // address arithmetic, their constants were kept in VGPRs across the whole unit loop)
+  int64_t row0 = 16 * W * ld, row1 = 16 * (7 - W) * ld, step = 4 * ld;
+  asm volatile("" : "+s"(row0), "+s"(row1), "+s"(step));
+  double* o = out + row0;
+#pragma unroll
+  for (int r = 0; r < 4; r++, o += step)
+#pragma unroll
+    for (int J = W; J < 8; J++) o[16 * J] = acc[J - W][r];
+  o = out + row1;
+#pragma unroll
+  for (int r = 0; r < 4; r++, o += step)
+#pragma unroll
+    for (int J = 7 - W; J < 8; J++) o[16 * J] = acc[1 + J][r];
+}
+
+// The stages [kstep0, kstep0 + nsteps) of a whole diagonal tile at column i0, then its store into
+// `out` (tile origin, pitch ld). Staging as tile_pass does it for a diagonal tile: the A strip only,
+// the same double buffer and one barrier per stage; each element's sum over k is in tile_pass's order
+// (the same stages and 4-deep MFMA steps), so it comes out with the same bits. One instantiation per
+// wave (the selection inside the loop made the compiler move the accumulators between two register
+// sets at every k-step); the four run the same barriers.
+template <int W>
+__device__ __forceinline__ void diag_tile_wave(const double* __restrict__ U, int64_t ldu, int64_t K, int64_t i0,
+                                          int64_t kstep0, int64_t nsteps, double* lds, double* __restrict__ out,
+                                          int64_t ld, int lane) {
+  auto stage_row = [&](int64_t kstep, int buf, int rr) {
+    const int r = W * (BK / 4) + rr;
+    const int64_t k = kstep * BK + r;
+    double* la = lds + buf * STAGE + r * LROW;
+    if (k < K)
+      __builtin_amdgcn_global_load_lds((const void*)(U + k * ldu + i0 + lane * 2), (void*)la, 16, 0, 0);
+    else
+      *reinterpret_cast<double2*>(la + lane * 2) = make_double2(0.0, 0.0);
+  };
+  d4 acc[9];
+#pragma unroll
+  for (int a = 0; a < 9; a++) acc[a] = (d4){0.0, 0.0, 0.0, 0.0};
+  if (nsteps > 0) {
+#pragma unroll
+    for (int rr = 0; rr < BK / 4; rr++) stage_row(kstep0, 0, rr);
+  }
+  __syncthreads();
+  for (int64_t st = 0; st < nsteps; st++) {
+    const int buf = (int)(st & 1);
+    if (st + 1 < nsteps) {
+#pragma unroll
+      for (int rr = 0; rr < BK / 4; rr++) stage_row(kstep0 + st + 1, buf ^ 1, rr);
+    }
+    const double* A = lds + buf * STAGE + (lane >> 4) * LROW + (lane & 15);
+#pragma unroll
+    for (int ks = 0; ks < BK / 4; ks++) diag_step<W>(A + ks * 4 * LROW, acc);
+    __syncthreads();
+  }
+  __syncthreads();
+  diag_store<W>(out + (lane >> 4) * ld + (lane & 15), ld, acc);
+}
+
+__device__ __forceinline__ void diag_tile(const double* __restrict__ U, int64_t ldu, int64_t K, int64_t i0,
+                                          int64_t kstep0, int64_t nsteps, double* lds, double* __restrict__ out,
+                                          int64_t ld, int wave, int lane) {
+  // the lane-derived addresses of this path are recomputed per unit: as invariants of the persistent
+  // unit loop they would be hoisted out of it and stay live through the off-diagonal units' MFMA loop
+  // (+10 VGPRs on the kernel)
+  asm volatile("" : "+v"(lane));
+  switch (wave) {  // wave-uniform (SGPR)
+    case 0: diag_tile_wave<0>(U, ldu, K, i0, kstep0, nsteps, lds, out, ld, lane); break;
+    case 1: diag_tile_wave<1>(U, ldu, K, i0, kstep0, nsteps, lds, out, ld, lane); break;
+    case 2: diag_tile_wave<2>(U, ldu, K, i0, kstep0, nsteps, lds, out, ld, lane); break;
+    default: diag_tile_wave<3>(U, ldu, K, i0, kstep0, nsteps, lds, out, ld, lane); break;
+  }
+}
+
 // Loci split of the GRM: every tile is cut into the same nslices stage ranges
 // [b[s], b[s+1]); workgroup (s, t) = blockIdx s * ntiles + t sums range s of tile t into slab
 // slot (s, t). The ranges shrink from first to last (plan() below), so the hardware's in-order
@@ -176,6 +276,8 @@ struct SliceBounds {
   // ticket sums the tile's slabs into G in range order (the reduce kernel's order), so grm_slab_reduce_kernel
   // is not launched
   int32_t fuse = 0;
+  // diag = 1 (GBM_GRM_DIAG): whole diagonal tiles compute only their 36 upper 16x16 blocks (diag_tile)
+  int32_t diag = 0;
 };
 
 // Ragged last tile column of the GRM: when n = 128 (nt − 1) + r with small r, the last tile
@@ -298,13 +400,23 @@ syrk_kernel(const double* __restrict__ U, int64_t ldu, int64_t K, int64_t c0, in
     const bool diag = (ti == tj);
     const int64_t i0 = c0 + ti * BT, j0 = c0 + tj * BT;
     const bool active = (i0 + wm * 64 < rlim) && (j0 + wn * 64 < rlim) && !(diag && wm == 1 && wn == 0);
+    const int64_t ks0 = sb.b[sl];
+    const int64_t ks1 = sb.b[sl + 1] < nst ? sb.b[sl + 1] : nst;
+    if constexpr (MODE != kPersistFused) {
+      // a whole diagonal tile with the slab or the direct epilogue: the upper 16x16 blocks only
+      // (ragged diagonal tiles, the carry and the fused reduce keep the quadrant form below)
+      if (diag && sb.diag && i0 + BT <= rlim && !(MODE == kSplit && sb.carry && sb.n > 1)) {
+        diag_tile(U, ldu, K, i0, ks0, ks1 > ks0 ? ks1 - ks0 : 0, lds,
+                  sb.n == 1 ? C + i0 * ldc + j0 : slab + ((int64_t)sl * ntiles + t) * (BT * BT), sb.n == 1 ? ldc : BT,
+                  wave, lane);
+        return;
+      }
+    }
     d4 acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
       for (int b = 0; b < 4; b++) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
-    const int64_t ks0 = sb.b[sl];
-    const int64_t ks1 = sb.b[sl + 1] < nst ? sb.b[sl + 1] : nst;
     tile_pass<false>(U, ldu, K, i0, j0, diag, active, ks0, ks1 > ks0 ? ks1 - ks0 : 0, lds, acc, wave, lane);
     if (MODE == kSplit && sb.carry && sb.n > 1) {  // (not compiled into the persistent kernel)
       // in-order carry: G tile = ((P_0 + P_1) + P_2) + ..., the same order (and rounding) as the
@@ -590,6 +702,9 @@ struct GrmTuning {
   bool persist = true;         // GBM_GRM_PERSIST: persistent workgroups with per-XCD queues
   bool edge_concurrent = true; // GBM_GRM_EDGE_CONCURRENT: edge kernel on the helper stream
   bool fuse = false;           // GBM_GRM_FUSED: the slab reduce inside the persistent tile kernel
+  bool diag = true;            // GBM_GRM_DIAG: whole diagonal tiles compute their upper 16x16 blocks only
+  double diag_cost = 0.66;     // GBM_GRM_DIAG_COST: the planner's cost of such a unit (off-diagonal = 1;
+                               // fitted on the C2 A/B against the quadrant form's 0.93)
   std::vector<double> split;   // GBM_GRM_SPLIT: relative loci-range sizes (tuning experiments)
 };
 
@@ -604,6 +719,12 @@ static GrmTuning grm_tuning() {
   t.persist = flag("GBM_GRM_PERSIST", true);
   t.edge_concurrent = flag("GBM_GRM_EDGE_CONCURRENT", true);
   t.fuse = flag("GBM_GRM_FUSED", false);
+  t.diag = flag("GBM_GRM_DIAG", true);
+  if (const char* e = ::gbm::knob("GBM_GRM_DIAG_COST")) {
+    const double c = atof(e);
+    if (c > 0.0 && c <= 1.0) t.diag_cost = c;
+  }
+  if (!t.diag) t.diag_cost = 0.93;  // the quadrant form: three of four quadrants, one SIMD idle
   if (const char* ov = ::gbm::knob("GBM_GRM_SPLIT")) {
     for (const char* q = ov; *q;) {
       char* end = nullptr;
@@ -670,7 +791,7 @@ static GrmPlan plan(int64_t n, int64_t p) {
   std::vector<double> cost;
   const int64_t R = resident_wgs();
   for (int64_t tj = 0; tj < nt; tj++)
-    for (int64_t ti = 0; ti <= tj; ti++) cost.push_back(ti == tj ? 0.93 : 1.0);
+    for (int64_t ti = 0; ti <= tj; ti++) cost.push_back(ti == tj ? tune.diag_cost : 1.0);
   g.ntiles = nt * (nt + 1) / 2;
   g.tile_elems = (int64_t)BT * BT;
   auto finish = [&](GrmPlan& gp) {
@@ -695,13 +816,14 @@ static GrmPlan plan(int64_t n, int64_t p) {
     }
     gp.persist = tune.persist && !gp.sb.carry;
     gp.sb.fuse = (gp.persist && gp.sb.n > 1 && tune.fuse) ? 1 : 0;
+    gp.sb.diag = tune.diag ? 1 : 0;
     // the ragged-column kernel and its reduce run on the helper stream, beside the persistent tiles
     gp.edge_concurrent = gp.sb.er > 0 && gp.persist && tune.edge_concurrent;
   };
   static std::mutex mu;
-  static std::map<std::tuple<int64_t, int64_t, int64_t, int, std::vector<double>>, SliceBounds> cache;
+  static std::map<std::tuple<int64_t, int64_t, int64_t, int, std::vector<double>, bool, double>, SliceBounds> cache;
   std::lock_guard<std::mutex> lock(mu);
-  auto key = std::make_tuple(nt, g.nst, R, tune.carry, tune.split);
+  auto key = std::make_tuple(nt, g.nst, R, tune.carry, tune.split, tune.diag, tune.diag_cost);
   auto it = cache.find(key);
   if (it != cache.end()) {
     g.sb = it->second;
