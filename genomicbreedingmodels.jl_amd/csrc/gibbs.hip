@@ -19,6 +19,10 @@
 // Random numbers: a counter-based hash of (seed, stream, counter) (no sampler state), Box-Muller
 // normals and Marsaglia-Tsang gammas, restated bit-for-bit in oracle/oracle.py (brr_*), so the
 // device chain and the oracle's un-blocked BGLR loop follow the same sample path.
+//
+// BayesA, BayesB and BayesC (gbm_bayes_fit, the models behind reference src/linear.jl:440-626) reuse
+// the per-launch skeleton, but their indicator draw is not affine in x_kᵀe: a block's 64 steps run
+// as a serial chain on the block's Gram matrix (bayes_chain_kernel, below brr_quantize_kernel).
 #include <atomic>
 #include <cmath>
 #include <map>
@@ -1587,6 +1591,333 @@ __global__ void __launch_bounds__(256) brr_quantize_kernel(const double* __restr
   if (nbad) atomicAdd(bad, nbad);
 }
 
+// ---- BayesA, BayesB, BayesC (include/gbm.h gbm_bayes_fit states the sampler) -----------------
+// Marker j has an effect b_j, an inclusion indicator d_j (BayesA: always 1) and (A, B) its own
+// variance varB_j. The indicator's probability is a non-linear function of x_jᵀe at the marker's
+// turn, so a block's 64 single-site steps are no triangular solve (no δ = M r̃): they run as a
+// serial chain on wave 0 of every chunk workgroup, lane k holding r_k = x_kᵀe + x2_k d_k b_k and
+// column k of the block's Gram matrix. bayes_prep_kernel forms, for every marker and in parallel,
+// everything of its step that does not depend on the chain (the normal, logit(u), 1/C, the square
+// roots), so that a chain step is FMAs, one compare, selects and one lane broadcast.
+constexpr int GBM_MODEL_A = 1, GBM_MODEL_B = 2, GBM_MODEL_C = 3;
+
+struct BayesState {
+  double mu, varE, varBc, S, pi;  // varBc: BayesC's common σ²_b
+  double S0e, df0, rate0, shape0, cIn, cOut;
+  double mubar, varEbar, varBbar, pibar;
+  int64_t it, burnin, thin, nsum;
+  uint64_t seed;
+  int model;
+};
+
+__device__ __forceinline__ bool bayes_accumulate(const BayesState* st) {
+  const int64_t i = st->it + 1;
+  return (i % st->thin == 0) && (i > st->burnin);
+}
+
+__device__ __forceinline__ double bayes_readlane(double v, int l) {
+  union {
+    double f;
+    int i[2];
+  } u;
+  u.f = v;
+  u.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
+  u.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
+  return u.f;
+}
+
+// the intercept step of brr_mu_kernel on the stream A = 8 it
+__global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, int64_t n,
+                                                        BayesState* __restrict__ st) {
+  __shared__ double red[16];
+  const double mu_old = st->mu;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) s += e[i] + mu_old;
+  s = brr_block_sum<1024>(s, red);
+  const double varE = st->varE;
+  const double mu = s / (double)n + sqrt(varE / (double)n) * brr_normal(st->seed, 8 * (uint64_t)st->it, 0xFFFFFFFFull);
+  for (int64_t i = threadIdx.x; i < n; i += 1024) e[i] = (e[i] + mu_old) - mu;
+  __syncthreads();
+  if (threadIdx.x == 0) st->mu = mu;
+}
+
+// Per marker j (one thread each, padded to whole blocks with zeros), the step constants pk[8 j ..]:
+//   0: x2 eff   1: eff = d b (old)   2: a = 1/(varE C)   3: c = sqrt(1/C) ξ   4: sqrt(varB) ξ
+//   5: b/(2 varE)   6: −b x2   7: log(π/(1−π)) − logit(u)
+// so that with r = x_jᵀe + x2 eff:  logOdds − logit(u) = pk5 (2 r + pk6) + pk7,  b_in = a r + c.
+// BayesA: pk5 = pk6 = 0, pk7 = 1 (always included).
+__global__ void __launch_bounds__(256) bayes_prep_kernel(int64_t p, int64_t ppad, const double* __restrict__ x2,
+                                                         const double* __restrict__ b, const double* __restrict__ d,
+                                                         const double* __restrict__ varB,
+                                                         const BayesState* __restrict__ st, double* __restrict__ pk) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= ppad) return;
+  double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (j < p) {
+    const int64_t par = st->it & 1;
+    const uint64_t A = 8 * (uint64_t)st->it;
+    const double varE = st->varE, iv = 1.0 / varE;
+    const double vb = st->model == GBM_MODEL_C ? st->varBc : varB[j];
+    const double bo = b[par * p + j], eff = d[par * p + j] * bo, xx = x2[j];
+    const double xi = brr_normal(st->seed, A, (uint64_t)j);
+    const double ic = 1.0 / (xx / varE + 1.0 / vb);
+    q[0] = xx * eff;
+    q[1] = eff;
+    q[2] = iv * ic;
+    q[3] = sqrt(ic) * xi;
+    q[4] = sqrt(vb) * xi;
+    if (st->model == GBM_MODEL_A) {
+      q[7] = 1.0;
+    } else {
+      const double u = brr_u01(st->seed, A + 3, (uint64_t)j), pi = st->pi;
+      q[5] = bo * (0.5 * iv);
+      q[6] = -bo * xx;
+      q[7] = log(pi / (1.0 - pi)) - log(u / (1.0 - u));
+    }
+  }
+  double2* out = reinterpret_cast<double2*>(pk + 8 * j);
+#pragma unroll
+  for (int u = 0; u < 4; u++) out[u] = make_double2(q[2 * u], q[2 * u + 1]);
+}
+
+// One block of 64 markers, brr_step_kernel's skeleton with the GEMV δ = M r̃ replaced by the serial
+// chain: d⁰ = Σ_c partial_in[c] (fixed order), r_k = d⁰_k + x2_k eff_k; step s broadcasts lane s's
+// δ_s = eff_s − d_new b_new and the lanes k > s do r_k += δ_s W[s][k] (lane k holds W[·][k] with
+// the entries s >= k zeroed, so a lane's r stops changing at its own step and its draw can be
+// formed again from it after the chain: same operands, same bits as the value it broadcast). Wave 0
+// of every workgroup runs the chain from identical inputs; then e += X_B δ and the next block's
+// partials as in brr_step_kernel. Workgroup 0 stores b, d and the running means of d b and d.
+template <typename T>
+__global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ Xt, int64_t ldx, int64_t n,
+                                                          int64_t p, double xs, const double* __restrict__ W,
+                                                          int64_t blk, int64_t nblk,
+                                                          const double* __restrict__ partial_in,
+                                                          double* __restrict__ partial_out,
+                                                          const double* __restrict__ pk, double* __restrict__ b,
+                                                          double* __restrict__ d, double* __restrict__ bbar,
+                                                          double* __restrict__ dbar, double* __restrict__ e,
+                                                          const BayesState* __restrict__ st) {
+  constexpr int RP = IW + 2;  // doubles (row pitch 2064 B, as brr_step_kernel)
+  __shared__ __attribute__((aligned(16))) double Xn[BB * RP];
+  __shared__ double delta[BB];
+  __shared__ double es[IW];
+  __shared__ double part4[4][BB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t j0 = blk * BB;
+  const int nb = (int)((p - j0) < BB ? (p - j0) : BB);
+  const int C = (int)gridDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * IW;
+  const int64_t i = i0 + tid;
+  const bool more = blk + 1 < nblk;
+  const int64_t j1 = j0 + BB;
+  const int nb1 = more ? (int)((p - j1) < BB ? (p - j1) : BB) : 0;
+  // (1) the next block's rows into LDS
+  uint8_t* Xb = reinterpret_cast<uint8_t*>(Xn);  // byte storage: rows of IW bytes, unpadded
+  if constexpr (sizeof(T) == 8) {
+    for (int q = wave; q < 2 * nb1; q += 4) {
+      const int k = q >> 1, h = q & 1;
+      const T* src = Xt + (j1 + k) * ldx + i0 + h * 128 + lane * 2;
+      __builtin_amdgcn_global_load_lds((const void*)src, (void*)(Xn + k * RP + h * 128), 16, 0, 0);
+    }
+  } else {
+    // 4 rows per wave instruction: lane = 16 (row within the four) + c writes LDS chunk c of its
+    // row, loaded from the row's 16-byte chunk c ^ (r & 15) (so chunk g of row r sits at position
+    // g ^ (r & 15) and the partials loop's lanes, one row each, read distinct banks). Rows past the
+    // block re-read row nb1 − 1: valid memory, never summed.
+    for (int q = wave; q < (nb1 + 3) / 4; q += 4) {
+      const int r = 4 * q + (lane >> 4), c = lane & 15;
+      const T* src = Xt + (j1 + (r < nb1 ? r : nb1 - 1)) * ldx + i0 + ((c ^ (r & 15)) * 16);
+      __builtin_amdgcn_global_load_lds((const void*)src, (void*)(Xb + q * 4 * IW), 16, 0, 0);
+    }
+  }
+  // (2) this thread's 64 genotypes of the block (rows past p clamped; their δ = 0)
+  double xv[BB];
+#pragma unroll
+  for (int s2 = 0; s2 < BB; s2++) xv[s2] = gval<T>(Xt[(j0 + (s2 < nb ? s2 : 0)) * ldx + i], xs);
+  const double e_old = e[i];
+  // (3) wave 0's operands: column `lane` of W (= its row: W is symmetric) and the step constants
+  double w[BB];
+  double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bool on = lane < nb;
+  const int64_t j = j0 + lane;
+  if (tid < 64) {
+    const double* wr = W + (blk * BB + lane) * BB;
+#pragma unroll
+    for (int s = 0; s < BB; s += 2) {
+      const double2 v = *reinterpret_cast<const double2*>(wr + s);
+      w[s] = v.x;
+      w[s + 1] = v.y;
+    }
+    const double2* pq = reinterpret_cast<const double2*>(pk + 8 * j);  // padded to whole blocks
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const double2 v = pq[u];
+      q[2 * u] = v.x;
+      q[2 * u + 1] = v.y;
+    }
+  }
+  const bool keeper = blockIdx.x == 0 && tid < 64 && on;
+  const double bb_old = keeper ? bbar[j] : 0.0, db_old = keeper ? dbar[j] : 0.0;
+  {
+    double a = 0.0;
+    for (int c0 = wave; c0 < C; c0 += 64) {
+      double v[16];
+#pragma unroll
+      for (int m = 0; m < 16; m++) v[m] = partial_in[min(c0 + 4 * m, C - 1) * BB + lane];  // unconditional loads
+#pragma unroll
+      for (int m = 0; m < 16; m++) a += c0 + 4 * m < C ? v[m] : 0.0;
+    }
+    part4[wave][lane] = a;
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const double d0 = ((part4[0][lane] + part4[1][lane]) + part4[2][lane]) + part4[3][lane];
+#pragma unroll
+    for (int s = 0; s < BB; s++) w[s] = lane > s ? w[s] : 0.0;
+    const double eff = q[1], qa = q[2], qc = q[3], bout = q[4], qbh = q[5], qm = q[6], qthr = q[7];
+    double r = d0 + q[0];
+#pragma unroll
+    for (int s = 0; s < BB; s++) {
+      const double lo = fma(qbh, fma(2.0, r, qm), qthr);
+      const double bin = fma(r, qa, qc);
+      const double cand = lo > 0.0 ? eff - bin : eff;
+      r = fma(bayes_readlane(cand, s), w[s], r);
+    }
+    const double lo = fma(qbh, fma(2.0, r, qm), qthr);
+    const double bin = fma(r, qa, qc);
+    const bool inc = lo > 0.0;
+    delta[lane] = inc ? eff - bin : eff;
+    if (keeper) {
+      const double bfin = inc ? bin : bout, dfin = inc ? 1.0 : 0.0;
+      const int64_t o = ((st->it & 1) ^ 1) * p + j;
+      b[o] = bfin;
+      d[o] = dfin;
+      if (bayes_accumulate(st)) {
+        const double k = (double)(st->nsum + 1);
+        bbar[j] = bb_old * ((k - 1.0) / k) + (inc ? bfin : 0.0) / k;
+        dbar[j] = db_old * ((k - 1.0) / k) + dfin / k;
+      }
+    }
+  }
+  __syncthreads();
+  double ei = 0.0;
+  if (i < n) {
+    double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+    for (int s2 = 0; s2 < BB; s2 += 2) {
+      acc0 = fma(delta[s2], xv[s2], acc0);
+      acc1 = fma(delta[s2 + 1], xv[s2 + 1], acc1);
+    }
+    ei = e_old + (acc0 + acc1);
+    e[i] = ei;
+  }
+  if (more) {
+    es[tid] = ei;
+    __syncthreads();  // also completes the global_load_lds of Xn
+    double s0 = 0.0, s1 = 0.0;
+    if (lane < nb1) {
+      const double* er = es + wave * 64;
+      if constexpr (sizeof(T) == 8) {
+        const double* xr = Xn + lane * RP + wave * 64;
+#pragma unroll
+        for (int u = 0; u < 64; u += 2) {
+          const double2 xv2 = *reinterpret_cast<const double2*>(xr + u);
+          s0 = fma(xv2.x, er[u], s0);
+          s1 = fma(xv2.y, er[u + 1], s1);
+        }
+      } else {
+        const uint8_t* xr = Xb + lane * IW;
+        uint4 v[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) v[t] = *reinterpret_cast<const uint4*>(xr + (((4 * wave + t) ^ (lane & 15)) * 16));
+        brr_dot64_u8(v, er, s0, s1);
+        s0 *= xs;
+        s1 *= xs;
+      }
+    }
+    part4[wave][lane] = s0 + s1;
+    __syncthreads();
+    if (tid < 64)
+      partial_out[blockIdx.x * BB + lane] = ((part4[0][lane] + part4[1][lane]) + part4[2][lane]) + part4[3][lane];
+  }
+}
+
+// Per-marker variances (BayesA, BayesB: varB_j = (S + b_j²)/χ²(df0 + 1) on the stream PM(it, j))
+// and, per workgroup, the partial sums vpart[5 blk ..] = Σ 1/varB_j, Σ d_j, Σ b_j², Σ varB_j over
+// its 256 markers and Σ e_i² over its 256 individuals (no atomics: bayes_final_kernel adds the
+// workgroups' partials in index order).
+__global__ void __launch_bounds__(256) bayes_var_kernel(const double* __restrict__ b, const double* __restrict__ d,
+                                                        double* __restrict__ varB, int64_t p,
+                                                        const double* __restrict__ e, int64_t n,
+                                                        const BayesState* __restrict__ st,
+                                                        double* __restrict__ vpart) {
+  __shared__ double red[4];
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t par = (st->it & 1) ^ 1;  // this iteration's samples
+  double v[5] = {0, 0, 0, 0, 0};
+  if (j < p) {
+    const double bj = b[par * p + j];
+    v[1] = d[par * p + j];
+    v[2] = bj * bj;
+    if (st->model != GBM_MODEL_C) {
+      const uint64_t pm = (1ull << 63) | ((uint64_t)st->it << 40) | (uint64_t)j;
+      const double vb = (st->S + v[2]) / brr_chisq(st->seed, pm, st->df0 + 1.0);
+      varB[j] = vb;
+      v[0] = 1.0 / vb;
+      v[3] = vb;
+    }
+  }
+  if (j < n) v[4] = e[j] * e[j];
+#pragma unroll
+  for (int u = 0; u < 5; u++) {
+    const double s = brr_block_sum<256>(v[u], red);
+    if (threadIdx.x == 0) vpart[5 * (int64_t)blockIdx.x + u] = s;
+  }
+}
+
+// The scalar draws of an iteration (one workgroup): S, BayesC's common varB, π, varE; the running
+// means of μ, varE, mean_j varB_j and π; next iteration.
+__global__ void __launch_bounds__(256) bayes_final_kernel(const double* __restrict__ vpart, int64_t nvb, int64_t p,
+                                                          int64_t n, BayesState* __restrict__ st) {
+  __shared__ double red[4];
+  double sum[5];
+#pragma unroll
+  for (int u = 0; u < 5; u++) {
+    double a = 0.0;
+    for (int64_t k = threadIdx.x; k < nvb; k += 256) a += vpart[5 * k + u];
+    sum[u] = brr_block_sum<256>(a, red);
+  }
+  if (threadIdx.x != 0) return;
+  const uint64_t A = 8 * (uint64_t)st->it, seed = st->seed;
+  const double df0 = st->df0, shape0 = st->shape0, rate0 = st->rate0;
+  double vbmean;
+  if (st->model == GBM_MODEL_C) {
+    const double vb = (sum[2] + st->S) / brr_chisq(seed, A + 1, df0 + (double)p);
+    st->varBc = vb;
+    st->S = brr_chisq(seed, A + 4, 2.0 * (0.5 * df0 + shape0)) / (2.0 * (1.0 / (2.0 * vb) + rate0));
+    vbmean = vb;
+  } else {
+    st->S = brr_chisq(seed, A + 4, 2.0 * (0.5 * (double)p * df0 + shape0)) / (2.0 * (0.5 * sum[0] + rate0));
+    vbmean = sum[3] / (double)p;
+  }
+  if (st->model != GBM_MODEL_A) {
+    const double m = sum[1];
+    const double g1 = 0.5 * brr_chisq(seed, A + 5, 2.0 * (m + st->cIn));
+    const double g2 = 0.5 * brr_chisq(seed, A + 6, 2.0 * (((double)p - m) + st->cOut));
+    st->pi = g1 / (g1 + g2);
+  }
+  st->varE = (sum[4] + st->S0e) / brr_chisq(seed, A + 2, df0 + (double)n);
+  if (bayes_accumulate(st)) {
+    const double k = (double)(st->nsum + 1);
+    st->mubar = st->mubar * ((k - 1.0) / k) + st->mu / k;
+    st->varEbar = st->varEbar * ((k - 1.0) / k) + st->varE / k;
+    st->varBbar = st->varBbar * ((k - 1.0) / k) + vbmean / k;
+    st->pibar = st->pibar * ((k - 1.0) / k) + st->pi / k;
+    st->nsum += 1;
+  }
+  st->it += 1;
+}
+
 }  // namespace
 }  // namespace gbm
 
@@ -1607,6 +1938,7 @@ struct BrrCtx {
   DevBuf Wsb, MS, Ssc, Pb, Rt, Dl, sbcnt;  // the super-block sweep
   DevBuf CS, CS2;                          // its cross-Grams C_s = X_sᵀ X_{s−1}, C2_s = X_sᵀ X_{s−2}
   DevBuf trace;                            // GBM_BRR_TRACE timestamps of this context's last sweep
+  DevBuf dind, dbar, varBj, pk, vpart, bst;  // gbm_bayes_fit: indicators, PIP, varB_j, step constants, partial sums, state
   hipGraphExec_t exec = nullptr;
   hipGraph_t graph = nullptr;
   std::vector<int64_t> key;  // what the captured graph was built for
@@ -1617,9 +1949,22 @@ struct BrrCtx {
     graph = nullptr;
     key.clear();
   }
+  // gbm_bayes_fit's captured iteration (its own slot: BRR and BayesA/B/C fits that alternate on
+  // one context keep both graphs)
+  hipGraphExec_t bayes_exec = nullptr;
+  hipGraph_t bayes_graph = nullptr;
+  std::vector<int64_t> bayes_key;
+  void drop_bayes_graph() {
+    if (bayes_exec) (void)hipGraphExecDestroy(bayes_exec);
+    if (bayes_graph) (void)hipGraphDestroy(bayes_graph);
+    bayes_exec = nullptr;
+    bayes_graph = nullptr;
+    bayes_key.clear();
+  }
   ~BrrCtx() {
     (void)hipSetDevice(dev);
     drop_graph();
+    drop_bayes_graph();
   }
 };
 
@@ -2100,4 +2445,234 @@ extern "C" int gbm_brr_fit(const double* X, int64_t n, int64_t p, int64_t ldx, c
                 "another process may share the device); the fit was re-run on the per-launch path");
   }
   return rc;
+}
+
+// One BayesA / BayesB / BayesC fit on a leased context (include/gbm.h gbm_bayes_fit): the setup of
+// brr_fit_impl (genotypes, column statistics, byte quantisation, Gram blocks), then per iteration
+// the linear chain prep, μ, block 0's partial dots, one chain launch per 64-marker block, the
+// variances — captured once as a graph and replayed. Never the super-block sweep or its lock; the
+// BRR path statistics are not written.
+static int bayes_fit_impl(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                          int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                          double counts, uint64_t seed, int dev, double* b_hat_out, double* y_pred_out,
+                          double* var_out, double* pip_out) {
+  using namespace gbm;
+  BrrLease lease;
+  GBM_TRY(brr_pool().acquire(dev, lease.c));
+  BrrCtx& cx = *lease.c;
+  GBM_HIP_TRY(hipSetDevice(dev));
+  hipStream_t s = cx.stream.s;
+  const int64_t npad = round_up(n, IW);
+  const int64_t C64 = (n + IW - 1) / IW;
+  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB;
+  const int64_t nvb = (std::max(n, p) + 255) / 256;
+  GBM_TRY(ensure(cx.Xt, dev, p * npad * 8));
+  GBM_TRY(ensure(cx.colmean, dev, p * 8));
+  GBM_TRY(ensure(cx.x2, dev, p * 8));
+  GBM_TRY(ensure(cx.e, dev, npad * 8));
+  GBM_TRY(ensure(cx.b, dev, 2 * p * 8));  // two copies (iteration parity), as are the indicators
+  GBM_TRY(ensure(cx.dind, dev, 2 * p * 8));
+  GBM_TRY(ensure(cx.bbar, dev, p * 8));
+  GBM_TRY(ensure(cx.dbar, dev, p * 8));
+  GBM_TRY(ensure(cx.varBj, dev, p * 8));
+  GBM_TRY(ensure(cx.pk, dev, ppad * 8 * 8));
+  GBM_TRY(ensure(cx.vpart, dev, nvb * 5 * 8));
+  GBM_TRY(ensure(cx.r, dev, 2 * C64 * BK2 * 8));  // ping-pong partial dots (BRR's size: one buffer, one pointer)
+  GBM_TRY(ensure(cx.bst, dev, sizeof(BayesState)));
+  GBM_TRY(ensure(cx.W, dev, nblk * BB * BB * 8));
+  GBM_HIP_TRY(hipMemsetAsync(cx.Xt.p, 0, (size_t)(p * npad * 8), s));
+  GBM_HIP_TRY(hipMemcpy2DAsync(cx.Xt.p, npad * 8, X, ldx * 8, n * 8, p, hipMemcpyHostToDevice, s));
+  brr_colstats_kernel<<<(unsigned)std::min<int64_t>(p, 4096), 256, 0, s>>>((const double*)cx.Xt.p, npad, p, n,
+                                                                           (double*)cx.colmean.p, (double*)cx.x2.p);
+  GBM_LAUNCH_CHECK();
+  std::vector<double> cm(p), xx(p);
+  GBM_HIP_TRY(hipMemcpyAsync(cm.data(), cx.colmean.p, p * 8, hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipMemcpyAsync(xx.data(), cx.x2.p, p * 8, hipMemcpyDeviceToHost, s));
+  // byte storage when X = D/s exactly, as brr_fit_impl (GBM_BRR_I8=0 keeps fp64 storage)
+  double xs = 0.0;
+  {
+    const char* ev = ::gbm::knob("GBM_BRR_I8");
+    if (!(ev && ev[0] == '0')) {
+      GBM_TRY(ensure(cx.D, dev, p * npad + 4096));
+      GBM_TRY(ensure(cx.badm, dev, sizeof(int)));
+      const double scales[3] = {2.0, 4.0, 1.0};
+      for (double sc : scales) {
+        int nbad = -1;
+        GBM_HIP_TRY(hipMemsetAsync(cx.badm.p, 0, sizeof(int), s));
+        brr_quantize_kernel<<<2048, 256, 0, s>>>((const double*)cx.Xt.p, p * npad, sc, (uint8_t*)cx.D.p, (int*)cx.badm.p);
+        GBM_LAUNCH_CHECK();
+        GBM_HIP_TRY(hipMemcpyAsync(&nbad, cx.badm.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        GBM_HIP_TRY(hipStreamSynchronize(s));
+        if (nbad == 0) {
+          xs = 1.0 / sc;
+          break;
+        }
+      }
+    }
+  }
+  brr_gram_kernel<<<(unsigned)nblk, 256, 0, s>>>((const double*)cx.Xt.p, npad, p, n, 1, (double*)cx.W.p);
+  GBM_LAUNCH_CHECK();
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  double ym = 0.0;
+  for (int64_t i = 0; i < n; i++) ym += y[i];
+  ym /= (double)n;
+  double vy = 0.0;
+  for (int64_t i = 0; i < n; i++) vy += (y[i] - ym) * (y[i] - ym);
+  vy /= (double)(n - 1);
+  double msx = 0.0, smsq = 0.0;
+  for (int64_t j = 0; j < p; j++) {
+    msx += xx[j];
+    smsq += cm[j] * cm[j];
+  }
+  msx = msx / (double)n - smsq;
+  if (!(msx > 0.0)) return fail(GBM_E_DATA, "gbm_bayes_fit: the markers have no variance");
+  const double shape0 = 1.1;
+  double S0 = vy * r2 / msx * (df0 + 2.0);
+  if (model != GBM_MODEL_A) S0 /= prob_in;
+  BayesState st0{};
+  st0.mu = ym;
+  st0.S0e = vy * (1.0 - r2) * (df0 + 2.0);
+  st0.varE = st0.S0e / (df0 + 2.0);
+  st0.S = S0;
+  st0.varBc = S0 / (df0 + 2.0);
+  st0.rate0 = (shape0 - 1.0) / S0;
+  st0.shape0 = shape0;
+  st0.df0 = df0;
+  st0.pi = prob_in;
+  st0.cIn = counts * prob_in;
+  st0.cOut = counts * (1.0 - prob_in);
+  st0.burnin = n_burnin;
+  st0.thin = thin;
+  st0.seed = seed;
+  st0.model = model;
+  std::vector<double> e0(npad, 0.0);
+  for (int64_t i = 0; i < n; i++) e0[i] = y[i] - ym;
+  std::vector<double> init(2 * p, 1.0);  // d = 1; then varB_j = S0/(df0 + 2)
+  GBM_HIP_TRY(hipMemcpyAsync(cx.e.p, e0.data(), npad * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.dind.p, init.data(), 2 * p * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  std::fill(init.begin(), init.begin() + p, st0.varBc);
+  GBM_HIP_TRY(hipMemcpyAsync(cx.varBj.p, init.data(), p * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemsetAsync(cx.b.p, 0, 2 * p * 8, s));
+  GBM_HIP_TRY(hipMemsetAsync(cx.bbar.p, 0, p * 8, s));
+  GBM_HIP_TRY(hipMemsetAsync(cx.dbar.p, 0, p * 8, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.bst.p, &st0, sizeof(BayesState), hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  auto* stp = (BayesState*)cx.bst.p;
+  const unsigned C = (unsigned)C64;
+  auto enqueue_iteration = [&]() -> int {
+    bayes_prep_kernel<<<(unsigned)(ppad / 256 + 1), 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
+                                                                 (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
+                                                                 (double*)cx.pk.p);
+    bayes_mu_kernel<<<1, 1024, 0, s>>>((double*)cx.e.p, n, stp);
+    if (xs > 0.0)
+      brr_dots0_kernel<uint8_t><<<C, 256, 0, s>>>((const uint8_t*)cx.D.p, npad, n, p, xs, (const double*)cx.e.p,
+                                                  (double*)cx.r.p);
+    else
+      brr_dots0_kernel<double><<<C, 256, 0, s>>>((const double*)cx.Xt.p, npad, n, p, 1.0, (const double*)cx.e.p,
+                                                 (double*)cx.r.p);
+    for (int64_t k = 0; k < nblk; k++) {
+      double* pin = (double*)cx.r.p + (k & 1) * (int64_t)C * BB;
+      double* pout = (double*)cx.r.p + ((k + 1) & 1) * (int64_t)C * BB;
+      if (xs > 0.0)
+        bayes_chain_kernel<uint8_t><<<C, 256, 0, s>>>((const uint8_t*)cx.D.p, npad, n, p, xs, (const double*)cx.W.p, k,
+                                                      nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
+                                                      (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+                                                      (double*)cx.e.p, stp);
+      else
+        bayes_chain_kernel<double><<<C, 256, 0, s>>>((const double*)cx.Xt.p, npad, n, p, 1.0, (const double*)cx.W.p, k,
+                                                     nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
+                                                     (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+                                                     (double*)cx.e.p, stp);
+    }
+    bayes_var_kernel<<<(unsigned)nvb, 256, 0, s>>>((const double*)cx.b.p, (const double*)cx.dind.p, (double*)cx.varBj.p, p,
+                                                   (const double*)cx.e.p, n, stp, (double*)cx.vpart.p);
+    bayes_final_kernel<<<1, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp);
+    return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, "gbm_bayes_fit: launch failed");
+  };
+  const std::vector<int64_t> key = {model, n, p, npad, (int64_t)(xs * 64.0),
+                                    (int64_t)(uintptr_t)cx.Xt.p, (int64_t)(uintptr_t)cx.D.p, (int64_t)(uintptr_t)cx.W.p,
+                                    (int64_t)(uintptr_t)cx.r.p, (int64_t)(uintptr_t)cx.e.p, (int64_t)(uintptr_t)cx.b.p,
+                                    (int64_t)(uintptr_t)cx.dind.p, (int64_t)(uintptr_t)cx.bbar.p,
+                                    (int64_t)(uintptr_t)cx.dbar.p, (int64_t)(uintptr_t)cx.varBj.p,
+                                    (int64_t)(uintptr_t)cx.pk.p, (int64_t)(uintptr_t)cx.vpart.p,
+                                    (int64_t)(uintptr_t)cx.x2.p, (int64_t)(uintptr_t)cx.bst.p};
+  int rc = GBM_OK;
+  if (cx.bayes_key != key) {
+    cx.drop_bayes_graph();
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+      rc = enqueue_iteration();
+      if (hipStreamEndCapture(s, &cx.bayes_graph) != hipSuccess || rc != GBM_OK ||
+          hipGraphInstantiate(&cx.bayes_exec, cx.bayes_graph, nullptr, nullptr, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        cx.drop_bayes_graph();
+        rc = GBM_OK;  // fall back to direct launches (same kernels, same order)
+      } else {
+        cx.bayes_key = key;
+      }
+    }
+  }
+  for (int64_t it = 0; it < n_iter && rc == GBM_OK; it++) {
+    if (cx.bayes_exec) {
+      if (hipGraphLaunch(cx.bayes_exec, s) != hipSuccess) rc = fail(GBM_E_HIP, "gbm_bayes_fit: graph launch failed");
+    } else {
+      rc = enqueue_iteration();
+    }
+  }
+  if (rc != GBM_OK) return rc;
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  BayesState fin{};
+  GBM_HIP_TRY(hipMemcpyAsync(&fin, cx.bst.p, sizeof(BayesState), hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipMemcpyAsync(b_hat_out + 1, cx.bbar.p, p * 8, hipMemcpyDeviceToHost, s));
+  if (pip_out) GBM_HIP_TRY(hipMemcpyAsync(pip_out, cx.dbar.p, p * 8, hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  b_hat_out[0] = fin.mubar;
+  if (var_out) {
+    var_out[0] = fin.varEbar;
+    var_out[1] = fin.varBbar;
+    var_out[2] = fin.pibar;
+  }
+  if (y_pred_out) {
+    const int64_t nchunks = predict_chunks(n, p);
+    GBM_TRY(ensure(cx.pb, dev, (p + 1) * 8));
+    GBM_TRY(ensure(cx.part, dev, nchunks * npad * 8));
+    GBM_TRY(ensure(cx.pout, dev, npad * 8));
+    GBM_HIP_TRY(hipMemcpyAsync(cx.pb.p, b_hat_out, (p + 1) * 8, hipMemcpyHostToDevice, s));
+    GBM_TRY(launch_predict((const double*)cx.Xt.p, npad, p, n, (const double*)cx.pb.p, p + 1, 1, (double*)cx.part.p,
+                           nchunks, (double*)cx.pout.p, npad, s));
+    GBM_HIP_TRY(hipMemcpyAsync(y_pred_out, cx.pout.p, n * 8, hipMemcpyDeviceToHost, s));
+    GBM_HIP_TRY(hipStreamSynchronize(s));
+  }
+  return GBM_OK;
+}
+
+extern "C" int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                             int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                             double counts, uint64_t seed, int device, double* b_hat_out, double* y_pred_out,
+                             double* var_out, double* pip_out) {
+  using namespace gbm;
+  RoctxRange r_("gbm_bayes_fit");
+  set_error("");
+  if (model != GBM_BAYES_A && model != GBM_BAYES_B && model != GBM_BAYES_C)
+    return fail(GBM_E_ARG, "gbm_bayes_fit: model must be GBM_BAYES_A, GBM_BAYES_B or GBM_BAYES_C");
+  if (!X || !y || !b_hat_out || n < 3 || p < 1 || ldx < n || n_iter < 1 || n_burnin < 0 || thin < 1 ||
+      !(r2 > 0.0 && r2 < 1.0) || !(df0 > 0.0))
+    return fail(GBM_E_ARG, "gbm_bayes_fit: bad arguments (n >= 3, p >= 1, ldx >= n, n_iter >= 1, n_burnin >= 0, "
+                           "thin >= 1, 0 < r2 < 1, df0 > 0)");
+  // the gamma sampler (Marsaglia-Tsang) needs shapes >= 1: (df0 + 1)/2 of the per-marker variances
+  // and counts·prob_in, counts·(1 − prob_in) of π's Beta draw
+  if (!(df0 >= 1.0) || !(prob_in > 0.0 && prob_in < 1.0) || !(counts * prob_in >= 1.0) ||
+      !(counts * (1.0 - prob_in) >= 1.0))
+    return fail(GBM_E_ARG, "gbm_bayes_fit: bad prior (df0 >= 1, 0 < prob_in < 1, counts*prob_in >= 1, "
+                           "counts*(1 - prob_in) >= 1)");
+  // the per-marker random streams are (iteration, marker) packed into 23 + 40 bits
+  if (n_iter > ((int64_t)1 << 23) || p >= ((int64_t)1 << 40))
+    return fail(GBM_E_ARG, "gbm_bayes_fit: n_iter <= 2^23 and p < 2^40");
+  if (n_iter <= n_burnin || (n_iter / thin) <= (n_burnin / thin))
+    return fail(GBM_E_ARG, "gbm_bayes_fit: no post-burn-in sample (need a multiple of thin in (n_burnin, n_iter])");
+  GBM_TRY(check_y(y, n, n, 1));
+  std::vector<int> devs;
+  GBM_TRY(check_devices(&device, 1, devs));
+  return bayes_fit_impl(model, X, n, p, ldx, y, n_iter, n_burnin, thin, r2, df0, prob_in, counts, seed, devs[0],
+                        b_hat_out, y_pred_out, var_out, pip_out);
 }

@@ -12,12 +12,12 @@ from .types import Fit, Genomes, Phenomes
 from .arrays import colstats, grm, grm_ploidy_aware, infer_ploidy
 from .session import GenotypeSession
 from .gwas import gwasols, gwasreml
-from .bayes import bayesian, brr_arrays
+from .bayes import bayes_arrays, bayesa, bayesb, bayesc, bayesian, brr_arrays
 from .cv import CV, cvbulk, cvbulk_setup, cvmultithread, fold_assignments, validate
 
 __all__ = [
     "ArgumentError", "GBMError", "device_count", "load_library",
     "gblup", "gblup_arrays", "gblup_dosage", "gblup_reml_arrays", "gblup_synthetic", "ridge", "ridge_path_cv", "ridge_select", "glmnet_folds", "metrics", "pearsonscorrelation", "r2", "heritabilitynarrow_sense",
     "LINEAR_MODELS", "extractxyetc", "predict", "Fit", "Genomes", "Phenomes", "colstats", "grm", "grm_ploidy_aware", "infer_ploidy",
-    "GenotypeSession", "gwasreml", "gwasols", "bayesian", "brr_arrays", "CV", "cvbulk", "cvbulk_setup", "cvmultithread", "fold_assignments", "validate",
+    "GenotypeSession", "gwasreml", "gwasols", "bayesian", "brr_arrays", "bayes_arrays", "bayesa", "bayesb", "bayesc", "CV", "cvbulk", "cvbulk_setup", "cvmultithread", "fold_assignments", "validate",
 ]

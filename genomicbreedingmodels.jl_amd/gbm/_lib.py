@@ -34,7 +34,7 @@ EXPORTS = (
     "gbm_dev_standardize_gather", "gbm_dev_gblup_terms",
     "gbm_session_create", "gbm_session_create_dosage_i8", "gbm_session_create_synthetic", "gbm_session_destroy", "gbm_session_gblup_fit",
     "gbm_session_predict", "gbm_session_reml_objective", "gbm_session_reml", "gbm_session_stats",
-    "gbm_session_ridge_path", "gbm_session_ridge_lambda_max", "gbm_brr_fit",
+    "gbm_session_ridge_path", "gbm_session_ridge_lambda_max", "gbm_brr_fit", "gbm_bayes_fit",
     "gbm_dev_chol_prepare", "gbm_dev_chol_prepare_cols", "gbm_dev_chol_group_size", "gbm_dev_chol_group", "gbm_dev_chol_factor_diag",
     "gbm_dev_chol_strip_doubles", "gbm_dev_chol_strip_pack", "gbm_dev_chol_strip_unpack", "gbm_dev_chol_finish",
     "gbm_dev_grm_packed_size", "gbm_dev_grm_pack", "gbm_dev_grm_unpack",
@@ -209,6 +209,8 @@ def _declare(lib):
     lib.gbm_dev_grm_unpack.argtypes = [P, I64, P, I64, P]
     lib.gbm_brr_fit.restype = I32
     lib.gbm_brr_fit.argtypes = [P, I64, I64, I64, P, I64, I64, I64, D, D, U64, I32, P, P, P]
+    lib.gbm_bayes_fit.restype = I32
+    lib.gbm_bayes_fit.argtypes = [I32, P, I64, I64, I64, P, I64, I64, I64, D, D, D, D, U64, I32, P, P, P, P]
     lib.gbm_debug_oom_retries.restype = I32
     lib.gbm_debug_oom_retries.argtypes = [P, P]
     lib.gbm_session_stats.restype = I32

@@ -1,6 +1,9 @@
 """``bayesian`` — mirror of reference src/bayes.jl:158-224 for ``bglr_model = "BRR"`` (Bayesian
 ridge regression), with the Gibbs sampler on the GPU (libgbm ``gbm_brr_fit``) instead of an
-Rscript/BGLR round trip (src/bayes.jl:28-105). SURVEY.md §8f row 3, config C4."""
+Rscript/BGLR round trip (src/bayes.jl:28-105). SURVEY.md §8f row 3, config C4.
+
+``bayesa``, ``bayesb``, ``bayesc`` — mirrors of the reference's model functions
+(src/linear.jl:440-626) over the BayesA / BayesB / BayesC samplers of libgbm ``gbm_bayes_fit``."""
 from __future__ import annotations
 
 import warnings
@@ -14,6 +17,7 @@ from .prediction import extractxyetc
 from .types import Fit, Genomes, Phenomes
 
 SUPPORTED = ("BRR",)
+BAYES_MODELS = {"BayesA": 1, "BayesB": 2, "BayesC": 3}  # include/gbm.h GBM_BAYES_*
 
 
 def brr_arrays(X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500, thin: int = 5,
@@ -40,9 +44,11 @@ def bayesian(bglr_model: str = "BRR", *, genomes: Genomes, phenomes: Phenomes, i
              idx_loci_alleles=None, idx_trait: int = 1, response_type: str = "gaussian", n_burnin: int = 500,
              n_iter: int = 1500, verbose: bool = False, thin: int = 5, seed: int = 42, device: int = 0) -> Fit:
     """Bayesian genomic prediction, same signature and Fit assembly as the reference
-    (src/bayes.jl:158-224). Only the Gaussian BRR model runs here."""
+    (src/bayes.jl:158-224). Only the Gaussian BRR model runs here; BayesA, BayesB and BayesC run
+    through the model functions ``bayesa``, ``bayesb`` and ``bayesc``."""
     if bglr_model not in SUPPORTED:
-        raise ArgumentError(f"bglr_model `{bglr_model}` is not available on the GPU path; supported: {SUPPORTED}")
+        hint = "; use gbm.bayesa, gbm.bayesb or gbm.bayesc for BayesA, BayesB, BayesC" if bglr_model in BAYES_MODELS else ""
+        raise ArgumentError(f"bglr_model `{bglr_model}` is not available through bayesian(); supported: {SUPPORTED}{hint}")
     if response_type != "gaussian":
         raise ArgumentError("only response_type = 'gaussian' is supported")
     X, y, entries, populations, loci_alleles = extractxyetc(
@@ -64,3 +70,71 @@ def bayesian(bglr_model: str = "BRR", *, genomes: Genomes, phenomes: Phenomes, i
     if not fit.checkdims():
         raise GBMError("Error fitting " + fit.model + ".")
     return fit
+
+
+def bayes_arrays(model: str, X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500, thin: int = 5,
+                 r2: float = 0.5, df0: float = 5.0, prob_in: float = 0.5, counts: float = 10.0, seed: int = 42,
+                 device: int = 0):
+    """Array-level BayesA / BayesB / BayesC Gibbs sampler (``model`` one of "BayesA", "BayesB", "BayesC").
+    Returns (b_hat (p+1,), y_pred (n,), [σ²_e, mean_j σ²_b_j, π] posterior means, pip (p,))."""
+    if model not in BAYES_MODELS:
+        raise ArgumentError(f"model `{model}` is not one of {tuple(BAYES_MODELS)}")
+    X = np.asfortranarray(np.asarray(X, dtype=np.float64))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    n, p = X.shape
+    b_hat = np.zeros(p + 1)
+    y_pred = np.zeros(n)
+    var = np.zeros(3)
+    pip = np.zeros(p)
+    lib = _lib.load()
+    rc = lib.gbm_bayes_fit(BAYES_MODELS[model], _lib.ptr(X), n, p, n, _lib.ptr(y), int(n_iter), int(n_burnin),
+                           int(thin), float(r2), float(df0), float(prob_in), float(counts),
+                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(device), _lib.ptr(b_hat), _lib.ptr(y_pred),
+                           _lib.ptr(var), _lib.ptr(pip))
+    _lib.check(rc, "gbm_bayes_fit")
+    return b_hat, y_pred, var, pip
+
+
+def _bayes_model_function(model: str, genomes: Genomes, phenomes: Phenomes, idx_entries, idx_loci_alleles,
+                          idx_trait: int, n_iter: int, n_burnin: int, verbose: bool) -> Fit:
+    """Fit assembly of ``bayesian`` (src/bayes.jl:158-224) for the three model functions."""
+    X, y, entries, populations, loci_alleles = extractxyetc(
+        genomes, phenomes, idx_entries=idx_entries, idx_loci_alleles=idx_loci_alleles, idx_trait=idx_trait,
+        add_intercept=False)
+    fit = Fit(n=X.shape[0], l=X.shape[1] + 1)
+    fit.model = model.lower()
+    fit.b_hat_labels = ["intercept"] + list(loci_alleles)
+    fit.trait = phenomes.traits[idx_trait - 1]
+    fit.entries = entries
+    fit.populations = populations
+    fit.y_true = y
+    b_hat, y_pred, var, pip = bayes_arrays(model, X, y, n_iter=n_iter, n_burnin=n_burnin)
+    fit.b_hat = b_hat
+    fit.y_pred = y_pred
+    fit.metrics = metrics(y, y_pred)
+    if verbose:
+        print(fit.metrics, "posterior means: varE", var[0], "mean varB", var[1], "pi", var[2], "mean PIP", pip.mean())
+    if not fit.checkdims():
+        raise GBMError("Error fitting " + fit.model + ".")
+    return fit
+
+
+def bayesa(*, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None, idx_trait: int = 1,
+           n_iter: int = 1500, n_burnin: int = 500, verbose: bool = False) -> Fit:
+    """BayesA (scaled-t marker effects), mirror of reference src/linear.jl:440-465."""
+    return _bayes_model_function("BayesA", genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, n_iter,
+                                 n_burnin, verbose)
+
+
+def bayesb(*, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None, idx_trait: int = 1,
+           n_iter: int = 1500, n_burnin: int = 500, verbose: bool = False) -> Fit:
+    """BayesB (point mass at zero + scaled-t slab), mirror of reference src/linear.jl:521-546."""
+    return _bayes_model_function("BayesB", genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, n_iter,
+                                 n_burnin, verbose)
+
+
+def bayesc(*, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None, idx_trait: int = 1,
+           n_iter: int = 1500, n_burnin: int = 500, verbose: bool = False) -> Fit:
+    """BayesC (point mass at zero + Gaussian slab), mirror of reference src/linear.jl:602-626."""
+    return _bayes_model_function("BayesC", genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, n_iter,
+                                 n_burnin, verbose)

@@ -150,6 +150,39 @@ function bglr_brr_gpu(; G::Matrix{Float64}, y::Vector{Float64}, n_iter::Int64 = 
     b_hat
 end
 
+# ---- BayesA / BayesB / BayesC (the models bglr() itself documents, src/bayes.jl:28-36)
+const GBM_BAYES_MODELS = Dict("BayesA" => Cint(1), "BayesB" => Cint(2), "BayesC" => Cint(3))  # include/gbm.h
+
+"""
+    bglr_gpu(; G, y, model="BayesA", response_type="gaussian", n_iter=1_500, n_burnin=500,
+             verbose=false, thin=5, seed=42, device=0)::Vector{Float64}
+
+`bglr`'s keyword signature (src/bayes.jl:28-36) over `gbm_bayes_fit`: returns `[posterior mean μ;
+posterior means of the marker effects d_j b_j]`, the vector `bglr` reads back from
+`c(sol\$mu, sol\$ETA\$MRK\$b)` (src/bayes.jl:83-104), so `bayesian` — and through it `bayesa`,
+`bayesb`, `bayesc` — uses it unchanged. Gaussian response only; BGLR's default priors
+(df0 = 5, R2 = 0.5, probIn = 0.5, counts = 10).
+"""
+function bglr_gpu(; G::Matrix{Float64}, y::Vector{Float64}, model::String = "BayesA",
+                  response_type::String = "gaussian", n_iter::Int64 = 1_500, n_burnin::Int64 = 500,
+                  verbose::Bool = false, thin::Int64 = 5, seed::UInt64 = UInt64(42), device::Integer = 0)
+    haskey(GBM_BAYES_MODELS, model) || throw(ArgumentError("bglr_gpu: model `$model` is not BayesA, BayesB or BayesC"))
+    response_type == "gaussian" || throw(ArgumentError("bglr_gpu: only response_type = \"gaussian\" runs on the GPU"))
+    n, p = size(G)
+    b_hat = zeros(p + 1)
+    var = zeros(3)
+    GC.@preserve G y b_hat var begin
+        rc = ccall((:gbm_bayes_fit, LIBGBM), Cint,
+                   (Cint, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64,
+                    Float64, Float64, UInt64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   GBM_BAYES_MODELS[model], G, n, p, stride(G, 2), y, n_iter, n_burnin, thin, 0.5, 5.0, 0.5, 10.0,
+                   seed, device, b_hat, C_NULL, var, C_NULL)
+    end
+    gbm_check(rc, "bglr_gpu")
+    verbose && @info "bglr_gpu posterior means" model varE = var[1] mean_varB = var[2] pi = var[3]
+    b_hat
+end
+
 # ---- ploidy-aware GRM -----------------------------------------------------------------------
 """
     grmploidyaware_gpu(X::Matrix{Float64}; ploidy=round(Int, 1 / minimum(X[X .!= 0.0])))

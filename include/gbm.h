@@ -541,6 +541,57 @@ int gbm_brr_fit(const double* X, int64_t n, int64_t p, int64_t ldx, const double
                 int64_t n_burnin, int64_t thin, double r2, double df0, uint64_t seed, int device,
                 double* b_hat_out, double* y_pred_out, double* var_out);
 
+/*
+ * ---- BayesA, BayesB and BayesC by Gibbs sampling ---------------------------------------------
+ * Replaces the Rscript/BGLR call of reference bglr()/bayesian() (src/bayes.jl:28-105) behind the
+ * model functions bayesa, bayesb and bayesc (src/linear.jl:440-626) for the Gaussian response.
+ * The sampler is BGLR 1.x's as restated here (BGLR is not vendored: sample-path parity with BGLR
+ * itself is unpinned); excluded effects are drawn from their prior and the indicator is drawn
+ * conditional on the current b_j.
+ *
+ * Priors: df0 (BGLR: 5), r2 (0.5), prob_in (0.5), counts (10); shape0 = 1.1.
+ * Initial state: vy = var(y) (ddof 1), x2_j = Σ_i x_ij², MSx = Σ_j x2_j/n − Σ_j mean_j²;
+ *   S0e = vy (1 − r2)(df0 + 2), varE = S0e/(df0 + 2);
+ *   S0 = vy r2/MSx (df0 + 2) (BayesA), that divided by prob_in (BayesB, BayesC);
+ *   S = S0, rate0 = (shape0 − 1)/S0, varB_j = S0/(df0 + 2) (BayesC: one common varB);
+ *   π = prob_in, cIn = counts prob_in, cOut = counts (1 − prob_in);
+ *   μ = mean(y), e = y − μ, b = 0, d = 1.
+ * Random numbers: counter-based u01 / normal / χ²(seed, stream, counter) as gbm_brr_fit's, with
+ *   Gamma(shape k, rate r) = χ²(2k)/(2r). Iteration `it` uses the streams A = 8 it: marker normals
+ *   (A, j), the μ normal (A, 0xFFFFFFFF); A+1: χ² of BayesC's varB; A+2: χ² of varE; A+3: the
+ *   indicator uniforms u_j = u01(A+3, j); A+4: the Gamma of S; A+5, A+6: the two Gammas of π's Beta
+ *   draw; and 2^63 | it 2^40 | j: the χ² of marker j's variance.
+ * One iteration:
+ *   1. μ ~ N(Σ(e + μ_old)/n, varE/n); e = (e + μ_old) − μ.
+ *   2. For j = 0 … p−1 in order: eff = d_j b_j, r = x_jᵀe + x2_j eff, ξ the marker's normal.
+ *      BayesA: d_new = 1. BayesB, BayesC: logOdds = log(π/(1−π)) + (2 b_j r − b_j² x2_j)/(2 varE),
+ *      d_new = [logOdds > log(u_j/(1−u_j))]. If d_new = 0: b_new = sqrt(varB_j) ξ; otherwise
+ *      C = x2_j/varE + 1/varB_j, b_new = (r/varE)/C + sqrt(1/C) ξ. Then e += (eff − d_new b_new) x_j,
+ *      b_j = b_new, d_j = d_new.
+ *   3. BayesA, BayesB: varB_j = (S + b_j²)/χ²(df0 + 1) for every j, then
+ *      S = Gamma(p df0/2 + shape0, Σ_j 1/varB_j / 2 + rate0). BayesC: varB = (Σ_j b_j² + S)/χ²(df0 + p)
+ *      over all b_j, then S = Gamma(df0/2 + shape0, 1/(2 varB) + rate0). BayesB, BayesC: m = Σ d_j,
+ *      g1 = Gamma(m + cIn, 1), g2 = Gamma(p − m + cOut, 1), π = g1/(g1 + g2).
+ *      All: varE = (Σe² + S0e)/χ²(df0 + n).
+ *   4. When (it + 1) % thin == 0 and it + 1 > n_burnin: running means of d_j b_j, d_j, μ, varE,
+ *      mean_j varB_j and π.
+ * b_hat_out (p+1) = [mean of μ; means of d_j b_j]; y_pred_out (n, optional) = b0 + X b;
+ * var_out (3, optional) = means of [varE, mean_j varB_j, π]; pip_out (p, optional) = means of d_j
+ * (the posterior inclusion probabilities; all 1 for BayesA). X column-major n x p.
+ * GBM_E_ARG for another model, gbm_brr_fit's argument checks, df0 < 1, prob_in outside (0, 1),
+ * counts prob_in < 1 or counts (1 − prob_in) < 1 (the gamma sampler needs shapes >= 1),
+ * n_iter > 2^23 or p >= 2^40 (the per-marker stream). One launch per 64-marker block (byte or fp64
+ * genotype storage as gbm_brr_fit: GBM_BRR_I8); never the super-block sweep.
+ */
+#define GBM_BAYES_A 1
+#define GBM_BAYES_B 2
+#define GBM_BAYES_C 3
+int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                  int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                  double counts, uint64_t seed, int device, double* b_hat_out /* p+1 */,
+                  double* y_pred_out /* n, may be NULL */, double* var_out /* 3; may be NULL */,
+                  double* pip_out /* p, may be NULL */);
+
 /* --------------------------------------------------------------------------------------
  * Diagnostics (tests and timing tools; no reference counterpart).
  * ------------------------------------------------------------------------------------ */
