@@ -124,6 +124,22 @@ int launch_gwas_stats(const double* W, int64_t ldw, int64_t rows, int64_t n, con
 int launch_center_columns(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz, double* mean,
                           double* sd, int32_t* keep, int64_t* q_dev, hipStream_t s);
 
+// Elastic-net coordinate descent on the packed active rows Za (enet.hip; driver: gbm_session_enet_path).
+// lda = enet_lda(n) (a multiple of the 256-individual chunk); the per-slot arrays (x2a, invden, b) and W are
+// padded to whole 64-marker blocks. launch_enet_pass: one pass, b_in → b_out, e in place, red[0] = the pass's
+// max x2 δ²/n and red[1] = ‖e‖²; `partial` holds 2 x ceil(n/256) x 64 doubles, blkmax one per block.
+int64_t enet_lda(int64_t n);
+int launch_enet_x2(const double* Z, int64_t ldz, int64_t p, int64_t n, double* x2, hipStream_t s);
+int launch_enet_gather(const double* Z, int64_t ldz, int64_t n, const int32_t* rows, int64_t a0, int64_t cnt,
+                       const double* x2, double* Za, int64_t lda, double* x2a, hipStream_t s);
+int64_t enet_gram_workspace(int64_t n);  // bytes of launch_enet_gram's ws (the Gram blocks' partial sums)
+int launch_enet_gram(const double* Za, int64_t lda, int64_t A, int64_t n, int64_t blk0, double* W, double* ws,
+                     hipStream_t s);
+int launch_enet_prep(int64_t A, const double* x2a, double l2, double* invden, hipStream_t s);
+int launch_enet_pass(const double* Za, int64_t lda, int64_t n, int64_t A, const double* W, const double* x2a,
+                     const double* invden, const double* b_in, double* b_out, double thr, double* partial,
+                     double* blkmax, double* e, double* red, hipStream_t s);
+int launch_enet_norm(const double* e, int64_t n, double* red, hipStream_t s);
 
 // REML choice of λ (session.cpp; reference loglikreml src/gwas.jl:450-483 with X = 1)
 struct RemlEval {

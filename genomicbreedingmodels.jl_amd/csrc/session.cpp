@@ -50,6 +50,10 @@ struct gbm_session {
   // the count of tested loci
   gbm::DevMem gwW, gwz, gwb, gwcnt;
   int64_t gww_bytes = 0;
+  // elastic-net path (gbm_session_enet_path): the packed active rows and their Gram blocks, the per-slot
+  // constants and coefficients (two copies, by pass parity), the residual, the per-locus x2, the chain's
+  // partial dots and block maxima, the pass scalars and the rows of one admission
+  gbm::DevBuf enZa, enW, enx2a, eninv, enb, ene, enx2, enpart, enblk, enred, enrows, engws;
 };
 
 namespace gbm {
@@ -679,6 +683,179 @@ extern "C" int gbm_session_ridge_path(gbm_session* s, const int64_t* idx, int64_
       for (int64_t i = 0; i < n_eval; i++) pred_out[k * n_eval + i] = all[idx_eval[i]];
     }
   }
+  return GBM_OK;
+}
+
+// ---- lasso / elastic-net path (glmnet alpha in (0, 1], standardize = false; reference lasso, src/linear.jl:333-343) --
+// Cyclic coordinate descent on an active set (include/gbm.h states the model and the schedule). Per λ: passes over
+// the packed active rows (one enet_chain_kernel launch per 64-marker block, one host synchronisation per pass for
+// the convergence scalar), then a screen g = Zᵀe over all p loci (gbm_dev_marker_effects) whose violators are
+// appended to the active list; b, e and the active list are carried from λ to λ on the device.
+extern "C" int gbm_session_enet_path(gbm_session* s, const int64_t* idx, int64_t n_train, const double* y, double alpha,
+                                     const double* lambdas, int64_t nl, double tol, int64_t max_passes, double dev_max,
+                                     double fdev, double* b_path_out, const int64_t* idx_eval, int64_t n_eval,
+                                     double* pred_out, int64_t* nl_done_out, double* dev_ratio_out, int64_t* passes_out,
+                                     int64_t* nnz_out) {
+  RoctxRange r_("gbm_session_enet_path");
+  set_error("");
+  if (!s || !y || !lambdas || nl < 1 || !b_path_out || (n_eval > 0 && (!idx_eval || !pred_out)))
+    return fail(GBM_E_ARG, "gbm_session_enet_path: bad arguments");
+  if (!(alpha > 0.0 && alpha <= 1.0))
+    return fail(GBM_E_ARG, "gbm_session_enet_path: alpha must be in (0, 1] (alpha = 0 is gbm_session_ridge_path, "
+                           "which solves that case exactly)");
+  for (int64_t k = 0; k < nl; k++) {
+    if (!(lambdas[k] > 0.0) || !std::isfinite(lambdas[k]))
+      return fail(GBM_E_ARG, "gbm_session_enet_path: lambdas must be finite and > 0");
+    if (k > 0 && lambdas[k] > lambdas[k - 1])
+      return fail(GBM_E_ARG, "gbm_session_enet_path: lambdas must be non-increasing (the path is warm-started)");
+  }
+  if (!(tol > 0.0) || !std::isfinite(tol) || max_passes < 1)
+    return fail(GBM_E_ARG, "gbm_session_enet_path: tol must be > 0 and max_passes >= 1");
+  if (std::isnan(dev_max) || !(fdev >= 0.0) || !std::isfinite(fdev))
+    return fail(GBM_E_ARG, "gbm_session_enet_path: dev_max must not be NaN and fdev must be finite and >= 0");
+  std::lock_guard<std::mutex> lock(s->mu);
+  GBM_HIP_TRY(hipSetDevice(s->dev));
+  GBM_TRY(check_y(y, n_train, n_train, 1));
+  if (n_eval > 0) GBM_TRY(check_idx(s, idx_eval, n_eval, "gbm_session_enet_path (eval)"));
+  GBM_TRY(ensure_training(s, idx, n_train, 1));
+  GBM_TRY(ensure_rhs(s, 1));
+  double ym = 0.0, yss = 0.0;
+  for (int64_t i = 0; i < n_train; i++) ym += y[i];
+  ym /= (double)n_train;
+  for (int64_t i = 0; i < n_train; i++) yss += (y[i] - ym) * (y[i] - ym);
+  const double ys = std::sqrt(yss / (double)n_train);
+  if (!(ys > 0.0)) return fail(GBM_E_ARG, "gbm_session_enet_path: y has zero variance");
+  hipStream_t st = s->stream.s;
+  const int64_t p = s->p, n = s->n, npad = s->npad, nT = s->nT;
+  const int64_t lda = enet_lda(nT), cap = std::min(p, 2 * s->npadT), cappad = round_up(cap, 64);
+  const int64_t C = (nT + 255) / 256;
+  GBM_TRY(ensure(s->enZa, s->dev, cap * lda * 8));
+  GBM_TRY(ensure(s->enW, s->dev, cappad * 64 * 8));
+  GBM_TRY(ensure(s->enx2a, s->dev, cappad * 8));
+  GBM_TRY(ensure(s->eninv, s->dev, cappad * 8));
+  GBM_TRY(ensure(s->enb, s->dev, 2 * cappad * 8));
+  GBM_TRY(ensure(s->ene, s->dev, lda * 8));
+  GBM_TRY(ensure(s->enx2, s->dev, p * 8));
+  GBM_TRY(ensure(s->enpart, s->dev, 2 * C * 64 * 8));
+  GBM_TRY(ensure(s->enblk, s->dev, (cappad / 64) * 8));
+  GBM_TRY(ensure(s->enred, s->dev, 2 * 8));
+  GBM_TRY(ensure(s->enrows, s->dev, cap * 4));
+  GBM_TRY(ensure(s->engws, s->dev, enet_gram_workspace(nT)));
+  const int64_t nchunks = predict_chunks(n, p);
+  if (n_eval > 0) {
+    GBM_TRY(dalloc(s->bvec, s->dev, (p + 1) * 8));
+    GBM_TRY(dalloc(s->part, s->dev, nchunks * npad * 8));
+    GBM_TRY(dalloc(s->pout, s->dev, npad * 8));
+  }
+  double* const Za = (double*)s->enZa.p;
+  double* const x2a = (double*)s->enx2a.p;
+  double* const bdev = (double*)s->enb.p;
+  double* const e = (double*)s->ene.p;
+  double* const red = (double*)s->enred.p;
+  std::vector<double> e0(lda, 0.0), x2h(p), meanh(p), g(p), bh(cap), all(n_eval > 0 ? npad : 0);
+  for (int64_t i = 0; i < nT; i++) e0[i] = y[i] - ym;
+  GBM_HIP_TRY(hipMemcpyAsync(e, e0.data(), lda * 8, hipMemcpyHostToDevice, st));
+  GBM_HIP_TRY(hipMemsetAsync(x2a, 0, cappad * 8, st));
+  GBM_HIP_TRY(hipMemsetAsync(bdev, 0, 2 * cappad * 8, st));
+  GBM_TRY(launch_enet_x2((const double*)s->Z.p, s->npadT, p, nT, (double*)s->enx2.p, st));
+  GBM_HIP_TRY(hipMemcpyAsync(x2h.data(), s->enx2.p, p * 8, hipMemcpyDeviceToHost, st));
+  GBM_HIP_TRY(hipMemcpyAsync(meanh.data(), s->mean.p, p * 8, hipMemcpyDeviceToHost, st));
+  GBM_HIP_TRY(hipStreamSynchronize(st));
+  std::vector<char> active(p, 0);
+  std::vector<int64_t> act;
+  std::vector<int32_t> fresh;
+  int par = 0;  // the copy of b that holds the current coefficients
+  int64_t done = 0, first_unconverged = -1;
+  double dev_prev = 0.0;
+  const int64_t mnl = std::min<int64_t>(5, nl);
+  for (int64_t k = 0; k < nl; k++) {
+    const double thr = (double)nT * lambdas[k] * alpha, l2 = (double)nT * lambdas[k] * (1.0 - alpha) / ys;
+    int64_t A = (int64_t)act.size(), passes = 0;
+    bool hit = false;
+    GBM_TRY(launch_enet_prep(A, x2a, l2, (double*)s->eninv.p, st));
+    for (;;) {
+      while (A > 0) {
+        if (passes >= max_passes) {
+          hit = true;
+          break;
+        }
+        double r2[2] = {0.0, 0.0};
+        GBM_TRY(launch_enet_pass(Za, lda, nT, A, (const double*)s->enW.p, x2a, (const double*)s->eninv.p,
+                                 bdev + par * cappad, bdev + (par ^ 1) * cappad, thr, (double*)s->enpart.p,
+                                 (double*)s->enblk.p, e, red, st));
+        par ^= 1;
+        GBM_HIP_TRY(hipMemcpyAsync(r2, red, 16, hipMemcpyDeviceToHost, st));
+        GBM_HIP_TRY(hipStreamSynchronize(st));
+        passes++;
+        if (r2[0] < tol * ys * ys) break;
+      }
+      if (hit) break;
+      // screen: g = Zᵀe over all p loci; every inactive locus past the threshold joins the list (ascending j)
+      GBM_TRY(gbm_dev_marker_effects((const double*)s->Z.p, s->npadT, p, nT, e, lda, 1, 1.0, nullptr,
+                                     (const double*)s->mean.p, (const double*)s->sd.p, (const int32_t*)s->keep.p,
+                                     (double*)s->B.p, p, (double*)s->msum.p, st));
+      GBM_HIP_TRY(hipMemcpyAsync(g.data(), s->B.p, p * 8, hipMemcpyDeviceToHost, st));
+      GBM_HIP_TRY(hipStreamSynchronize(st));
+      fresh.clear();
+      for (int64_t j = 0; j < p; j++)
+        if (!active[j] && std::fabs(g[j]) > thr && x2h[j] > 0.0) fresh.push_back((int32_t)j);
+      if (fresh.empty()) break;
+      const int64_t cnt = (int64_t)fresh.size();
+      if (A + cnt > cap)
+        return fail(GBM_E_ARG, "gbm_session_enet_path: the active set needs " + std::to_string(A + cnt) +
+                                   " markers at lambda number " + std::to_string(k + 1) + ", over the cap of min(p, 2 npad) = " +
+                                   std::to_string(cap) + " packed rows (use a larger lambda or alpha)");
+      GBM_HIP_TRY(hipMemcpyAsync(s->enrows.p, fresh.data(), cnt * 4, hipMemcpyHostToDevice, st));
+      GBM_TRY(launch_enet_gather((const double*)s->Z.p, s->npadT, nT, (const int32_t*)s->enrows.p, A, cnt,
+                                 (const double*)s->enx2.p, Za, lda, x2a, st));
+      GBM_HIP_TRY(hipStreamSynchronize(st));  // `fresh` is pageable: the copy has read it before it changes
+      for (int32_t j : fresh) {
+        active[j] = 1;
+        act.push_back(j);
+      }
+      const int64_t blk0 = A / 64;  // the partly filled last block and the new ones
+      A += cnt;
+      GBM_TRY(launch_enet_gram(Za, lda, A, nT, blk0, (double*)s->enW.p, (double*)s->engws.p, st));
+      GBM_TRY(launch_enet_prep(A, x2a, l2, (double*)s->eninv.p, st));
+    }
+    if (hit && first_unconverged < 0) first_unconverged = k;
+    double r2[2] = {0.0, 0.0};
+    GBM_TRY(launch_enet_norm(e, nT, red, st));
+    GBM_HIP_TRY(hipMemcpyAsync(r2, red, 16, hipMemcpyDeviceToHost, st));
+    if (A > 0) GBM_HIP_TRY(hipMemcpyAsync(bh.data(), bdev + par * cappad, A * 8, hipMemcpyDeviceToHost, st));
+    GBM_HIP_TRY(hipStreamSynchronize(st));
+    double* bk = b_path_out + k * (p + 1);
+    std::fill(bk, bk + p + 1, 0.0);
+    double msum = 0.0;
+    int64_t nnz = 0;
+    for (int64_t a = 0; a < A; a++) {
+      bk[1 + act[a]] = bh[a];
+      msum += meanh[act[a]] * bh[a];
+      nnz += bh[a] != 0.0;
+    }
+    bk[0] = ym - msum;
+    const double dev = 1.0 - r2[1] / yss;
+    if (dev_ratio_out) dev_ratio_out[k] = dev;
+    if (passes_out) passes_out[k] = passes;
+    if (nnz_out) nnz_out[k] = nnz;
+    if (n_eval > 0) {
+      GBM_HIP_TRY(hipMemcpyAsync(s->bvec.p, bk, (p + 1) * 8, hipMemcpyHostToDevice, st));
+      GBM_TRY(launch_predict((const double*)s->Xt.p, npad, p, n, (const double*)s->bvec.p, p + 1, 1,
+                             (double*)s->part.p, nchunks, (double*)s->pout.p, npad, st));
+      GBM_HIP_TRY(hipMemcpyAsync(all.data(), s->pout.p, npad * 8, hipMemcpyDeviceToHost, st));
+      GBM_HIP_TRY(hipStreamSynchronize(st));
+      for (int64_t i = 0; i < n_eval; i++) pred_out[k * n_eval + i] = all[idx_eval[i]];
+    }
+    done = k + 1;
+    // glmnet's early stop: the λ that trips it is the last one kept
+    if (done >= mnl && (dev > dev_max || (fdev > 0.0 && dev - dev_prev < fdev * dev))) break;
+    dev_prev = dev;
+  }
+  if (nl_done_out) *nl_done_out = done;
+  if (first_unconverged >= 0)
+    set_error("warning: gbm_session_enet_path: max_passes = " + std::to_string(max_passes) +
+              " reached before convergence, first at lambda number " + std::to_string(first_unconverged + 1) +
+              " (the coefficients returned there are the last pass's)");
   return GBM_OK;
 }
 

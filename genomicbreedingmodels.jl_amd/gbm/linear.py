@@ -254,3 +254,85 @@ def ridge(*, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_al
     if not fit.checkdims():
         raise GBMError("Error fitting " + fit.model + ".")
     return fit
+
+
+def enet_path_cv(X: np.ndarray, y: np.ndarray, alpha: float = 1.0, *, nlambda: int = 100,
+                 lambda_min_ratio: float = 0.01, tol: float = 1e-7, max_passes: int = 1_000_000,
+                 nfolds: int | None = None, seed: int = 42, device: int = 0):
+    """``GLMNet.glmnetcv(X, y, alpha=alpha, standardize=false, nlambda=100, lambda_min_ratio=0.01, tol=1e-7,
+    intercept=true)`` as called by reference lasso (src/linear.jl:333-343), on the GPU: the λ path from the
+    full data by coordinate descent with glmnet's early stop, then every fold at the λ kept with the early
+    stop off, k-fold CV mean squared error per λ. Returns dict(lambda, a0, betas (p, nl), meanloss,
+    dev_ratio, nnz) over the nl λ kept."""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    n = X.shape[0]
+    nf = nfolds if nfolds is not None else min(10, n // 3)
+    if nf < 2:
+        raise ArgumentError("glmnetcv needs at least 2 folds (n >= 6)")
+    from .session import GenotypeSession
+    with GenotypeSession(X, device=device) as s:
+        idx = np.arange(n)
+        lmax = s.ridge_lambda_max(idx, y) * 1e-3 / max(alpha, 1e-3)
+        lam = lmax * lambda_min_ratio ** (np.arange(nlambda) / (nlambda - 1))
+        full = s.enet_path(idx, y, lam, alpha=alpha, tol=tol, max_passes=max_passes)
+        lam = full["lambdas"]
+        folds = glmnet_folds(n, nf, np.random.default_rng(seed))
+        loss = np.zeros((lam.size, nf))
+        for f in range(1, nf + 1):
+            tr, ho = np.flatnonzero(folds != f), np.flatnonzero(folds == f)
+            r = s.enet_path(tr, y[tr], lam, alpha=alpha, tol=tol, max_passes=max_passes, idx_eval=ho,
+                            early_stop=False)
+            loss[:, f - 1] = ((r["pred"] - y[ho, None]) ** 2).mean(axis=0)
+    path = full["b_path"]
+    return {"lambda": lam.copy(), "a0": path[0].copy(), "betas": path[1:].copy(), "meanloss": loss.mean(axis=1),
+            "dev_ratio": full["dev_ratio"].copy(), "nnz": full["nnz"].copy()}
+
+
+def lasso_select(a0: np.ndarray, betas: np.ndarray, meanloss: np.ndarray) -> np.ndarray:
+    """The coefficient choice of reference lasso (src/linear.jl:352-360): λs sorted by CV loss, the first
+    solution whose slopes have variance (ddof 1) >= 1e-10 kept, its intercept ``a0[idx_sort][i]``. (Not
+    ridge's loop: no double permutation and no last-λ clause.) Where no solution has slope variance the
+    reference indexes past the end; here that is a GBMError."""
+    idx_sort = np.argsort(meanloss, kind="stable")
+    intercepts = a0[idx_sort]
+    sorted_betas = betas[:, idx_sort]
+    nl = betas.shape[1]
+    b_hat = np.zeros(betas.shape[0] + 1)
+    i = 0
+    while np.var(b_hat[1:], ddof=1) < 1e-10:
+        if i >= nl:
+            raise GBMError("lasso: no solution on the path has slope variance >= 1e-10 (the reference indexes "
+                           "past the end of the path here, src/linear.jl:357-360)")
+        b_hat = np.concatenate([[intercepts[i]], sorted_betas[:, i]])
+        i += 1
+    return b_hat
+
+
+def lasso(*, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None, idx_trait: int = 1,
+          verbose: bool = False, seed: int = 42, device: int = 0) -> Fit:
+    """Mirror of reference ``lasso`` (src/linear.jl:302-378) with the GLMNet path on the GPU."""
+    X, y, entries, populations, loci_alleles = extractxyetc(
+        genomes, phenomes, idx_entries=idx_entries, idx_loci_alleles=idx_loci_alleles,
+        idx_trait=idx_trait, add_intercept=False)
+    fit = Fit(n=X.shape[0], l=X.shape[1])
+    fit.model = "lasso"
+    fit.b_hat_labels = ["intercept"] + list(loci_alleles)
+    fit.trait = phenomes.traits[idx_trait - 1]
+    fit.entries = entries
+    fit.populations = populations
+    fit.y_true = y
+    cv = enet_path_cv(X, y, alpha=1.0, seed=seed, device=device)
+    b_hat = lasso_select(cv["a0"], cv["betas"], cv["meanloss"])
+    from .session import GenotypeSession
+    with GenotypeSession(X, device=device) as s:
+        y_pred = s.predict(np.arange(X.shape[0]), b_hat)
+    fit.b_hat = b_hat
+    fit.y_pred = y_pred
+    fit.metrics = metrics(y, y_pred)
+    if verbose:
+        print("argmin =", int(np.argmin(cv["meanloss"])) + 1)
+        print(fit.metrics)
+    if not fit.checkdims():
+        raise GBMError("Error fitting " + fit.model + ".")
+    return fit

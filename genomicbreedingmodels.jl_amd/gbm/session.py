@@ -226,6 +226,35 @@ class GenotypeSession:
         _lib.check(rc, "gbm_session_ridge_path")
         return b
 
+    def enet_path(self, idx, y, lambdas, alpha: float = 1.0, tol: float = 1e-7, max_passes: int = 1_000_000,
+                  idx_eval=None, early_stop: bool = True) -> dict:
+        """glmnet lasso / elastic-net solutions (alpha in (0, 1], standardize = false, intercept) on rows
+        ``idx`` along the non-increasing ``lambdas``, by coordinate descent on the device
+        (gbm_session_enet_path). ``early_stop``: glmnet's rule (dev_max = 0.999, fdev = 1e-5); off, every λ is
+        solved. Returns dict(b_path (p+1, nl_done) [intercept first], lambdas (the λ kept), dev_ratio, passes,
+        nnz, nl_done, warning (None or the library's message) and, with ``idx_eval``, pred (n_eval, nl_done))."""
+        idx = _idx(idx)
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+        lam = np.ascontiguousarray(np.atleast_1d(np.asarray(lambdas, dtype=np.float64)))
+        nl = lam.size
+        b = np.zeros((self.p + 1, nl), order="F")
+        dev, passes, nnz, done = np.zeros(nl), np.zeros(nl, dtype=np.int64), np.zeros(nl, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        ie = _idx(idx_eval) if idx_eval is not None else None
+        pred = np.zeros((ie.size, nl), order="F") if ie is not None else None
+        dev_max, fdev = (0.999, 1e-5) if early_stop else (float("inf"), 0.0)
+        rc = self.lib.gbm_session_enet_path(self._h, _lib.ptr(idx), idx.size, _lib.ptr(y), float(alpha), _lib.ptr(lam),
+                                            nl, float(tol), int(max_passes), dev_max, fdev, _lib.ptr(b),
+                                            _lib.ptr(ie), 0 if ie is None else ie.size, _lib.ptr(pred),
+                                            _lib.ptr(done), _lib.ptr(dev), _lib.ptr(passes), _lib.ptr(nnz))
+        _lib.check(rc, "gbm_session_enet_path")
+        k = int(done[0])
+        msg = _lib.last_error()
+        out = {"b_path": b[:, :k], "lambdas": lam[:k], "dev_ratio": dev[:k], "passes": passes[:k], "nnz": nnz[:k],
+               "nl_done": k, "warning": msg if msg.startswith("warning:") else None}
+        if pred is not None:
+            out["pred"] = pred[:, :k]
+        return out
+
     def stats(self):
         """(GRM builds, GRM cache hits)."""
         v = np.zeros(2, dtype=np.int64)

@@ -192,3 +192,99 @@ function gwasols_gpu(; genomes::Genomes, phenomes::Phenomes, idx_entries = nothi
     checkdims(fit) || throw(ErrorException("Error performing GWAS via OLS on the GPU."))
     fit
 end
+
+# ---- lasso on the GPU (gbm_session_enet_path; untested here like the rest of this file: no Julia in the
+# build container; the Python mirror gbm/linear.py `lasso` drives the same ccall) --------------------------
+# One elastic-net path call on the rows idx (0-based) of the session h: (b_path (p+1) x nl_done, pred, nl_done).
+function gbm_enet_path(h::Ptr{Cvoid}, p::Integer, idx::Vector{Int64}, y::Vector{Float64}, λ::Vector{Float64};
+                       alpha::Float64 = 1.0, tol::Float64 = 1e-7, max_passes::Int64 = 1_000_000,
+                       idx_eval::Vector{Int64} = Int64[], early_stop::Bool = true)
+    nl = length(λ)
+    path = zeros(p + 1, nl)
+    pred = zeros(length(idx_eval), nl)
+    done = zeros(Int64, 1)
+    dev_max, fdev = early_stop ? (0.999, 1e-5) : (Inf, 0.0)
+    GC.@preserve idx y λ path pred idx_eval done begin
+        gbm_check(ccall((:gbm_session_enet_path, LIBGBM), Cint,
+                        (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Float64, Int64,
+                         Float64, Float64, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64},
+                         Ptr{Int64}, Ptr{Int64}),
+                        h, idx, length(idx), y, alpha, λ, nl, tol, max_passes, dev_max, fdev, path,
+                        isempty(idx_eval) ? Ptr{Int64}(C_NULL) : pointer(idx_eval), length(idx_eval),
+                        isempty(idx_eval) ? Ptr{Float64}(C_NULL) : pointer(pred), done, C_NULL, C_NULL, C_NULL),
+                  "enet_path")
+    end
+    msg = gbm_last_error()
+    startswith(msg, "warning:") && @warn msg
+    k = done[1]
+    (path = path[:, 1:k], pred = pred[:, 1:k], nl_done = k)
+end
+
+"""
+    lasso_gpu(; genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, verbose=false)::Fit
+
+`lasso` (src/linear.jl:302-378) with `GLMNet.glmnetcv(alpha = 1.0, standardize = false, nlambda = 100,
+lambda_min_ratio = 0.01, tol = 1e-7, intercept = true)` replaced by the coordinate-descent path on the GPU:
+the full-data path with glmnet's early stop, GLMNet.jl's folds at the λ kept with the stop off, the mean
+squared error per λ, then the reference's own selection loop (src/linear.jl:352-360) and Fit assembly.
+"""
+function lasso_gpu(; genomes::Genomes, phenomes::Phenomes, idx_entries = nothing, idx_loci_alleles = nothing,
+                   idx_trait::Int64 = 1, verbose::Bool = false, device::Integer = 0)::Fit
+    X, y, entries, populations, loci_alleles = extractxyetc(genomes, phenomes, idx_entries = idx_entries,
+                                                            idx_loci_alleles = idx_loci_alleles, idx_trait = idx_trait,
+                                                            add_intercept = false)
+    n, p = size(X)
+    fit = Fit(n = n, l = p)
+    fit.model = "lasso"
+    fit.b_hat_labels = vcat(["intercept"], loci_alleles)
+    fit.trait = phenomes.traits[idx_trait]
+    fit.entries = entries
+    fit.populations = populations
+    fit.y_true = y
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    gbm_check(ccall((:gbm_session_create, LIBGBM), Cint,
+                    (Ptr{Float64}, Int64, Int64, Int64, Cint, Ptr{Ptr{Cvoid}}), X, n, p, n, device, h),
+              "lasso (session)")
+    local a0, betas, meanloss
+    try
+        all = collect(Int64, 0:(n-1))
+        lmax = Ref(0.0)
+        gbm_check(ccall((:gbm_session_ridge_lambda_max, LIBGBM), Cint,
+                        (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}), h[], all, n, y, lmax),
+                  "ridge_lambda_max")
+        λ = collect((lmax[] * 1e-3) .* 0.01 .^ ((0:99) ./ 99))  # alpha = 1: glmnet's λ_max is the alpha = 0 one · 1e-3
+        full = gbm_enet_path(h[], p, all, y, λ)
+        λ = λ[1:full.nl_done]
+        nfolds = min(10, div(n, 3))
+        q, r = divrem(n, nfolds)
+        folds = shuffle!([repeat(1:nfolds, outer = q); 1:r])  # GLMNet.jl's default folds
+        loss = zeros(length(λ), nfolds)
+        for f = 1:nfolds
+            tr = findall(folds .!= f) .- 1
+            ho = findall(folds .== f) .- 1
+            res = gbm_enet_path(h[], p, tr, y[tr .+ 1], λ; idx_eval = ho, early_stop = false)
+            loss[:, f] = vec(mean((res.pred .- y[ho .+ 1]) .^ 2, dims = 1))
+        end
+        a0, betas, meanloss = full.path[1, :], full.path[2:end, :], vec(mean(loss, dims = 2))
+    finally
+        ccall((:gbm_session_destroy, LIBGBM), Cvoid, (Ptr{Cvoid},), h[])
+    end
+    verbose && println(string("argmin = ", argmin(meanloss)))
+    # Use the coefficients with variance (src/linear.jl:352-360)
+    b_hat::Vector{Float64} = zeros(p + 1)
+    idx_sort = sortperm(meanloss)
+    INTERCEPTSs = a0[idx_sort]
+    BETAs = betas[:, idx_sort]
+    i = 1
+    while var(b_hat[2:end]) < 1e-10
+        b_hat = vcat(INTERCEPTSs[i], BETAs[:, i])
+        i += 1
+    end
+    y_pred::Vector{Float64} = b_hat[1] .+ (X * b_hat[2:end])
+    fit.b_hat = b_hat
+    fit.metrics = metrics(y, y_pred)
+    fit.y_pred = y_pred
+    verbose && println(fit.metrics)
+    checkdims(fit) || throw(ErrorException("Error fitting " * fit.model * "."))
+    fit
+end

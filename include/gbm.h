@@ -494,6 +494,44 @@ int gbm_session_ridge_path(gbm_session* s, const int64_t* idx, int64_t n_train, 
 /* glmnet's largest λ for alpha = 0 (alpha floored at 1e-3): max_j |x_cjᵀ(y − ȳ)| / n / 1e-3. */
 int gbm_session_ridge_lambda_max(gbm_session* s, const int64_t* idx, int64_t n_train, const double* y,
                                  double* lambda_max);
+/*
+ * Lasso / elastic-net path of reference lasso (GLMNet alpha = 1, standardize = false, intercept;
+ * src/linear.jl:333-343) on the rows idx[0..n_train), by cyclic coordinate descent on an active set.
+ * (Additive: GBM_VERSION stays 212.)
+ *
+ * Model, for alpha in (0, 1] and a user λ (glmnet's elastic net; σ_y = the population sd of the training y,
+ * by which glmnet's elnet divides λ): minimise
+ *   (1/2n)‖y − a0 − Xb‖² + λ alpha ‖b‖₁ + (λ (1 − alpha)/(2 σ_y)) ‖b‖².
+ * With x_j the centred column, x2_j = x_jᵀx_j, e the residual, thr = n λ alpha and
+ * den_j = x2_j + n λ (1 − alpha)/σ_y, one coordinate step is
+ *   g = x_jᵀe + x2_j b_j;  b_new = sign(g) max(|g| − thr, 0)/den_j;  e += (b_j − b_new) x_j.
+ * A column with x2_j = 0 keeps b_j = 0 and is never admitted (glmnet's ju = 0). a0 = ȳ − Σ_j mean_j b_j.
+ * alpha = 0 is refused (GBM_E_ARG): gbm_session_ridge_path solves that case exactly.
+ *
+ * Schedule per λ (warm start: b, e and the active list are carried from the previous λ on the device):
+ *   1. coordinate-descent passes over the active list (in order of admission; within one screen ascending j)
+ *      until a pass's max_j (x2_j/n) δ_j² < tol σ_y², or max_passes passes were run at this λ;
+ *   2. screen g = Zᵀe over all p loci: every inactive j with |g_j| > thr and x2_j > 0 is admitted;
+ *   3. if any was admitted go to 1, else this λ is done.
+ * An empty active list skips step 1. The active list never shrinks and is capped at min(p, 2 gbm_dev_npad(n_train))
+ * markers: a fit that needs more returns GBM_E_ARG.
+ * Early stop (glmnet's elnet): with mnl = min(5, nl), after λ number k >= mnl (from 1) the path stops when
+ * dev_k > dev_max or (fdev > 0 and dev_k − dev_{k−1} < fdev dev_k), dev_0 = 0; that λ is the last one kept.
+ * glmnet's values are dev_max = 0.999, fdev = 1e-5; fdev = 0 with dev_max = +inf disables the rule.
+ *
+ * lambdas: nl values, finite, > 0, non-increasing. tol > 0, max_passes >= 1. Outputs as gbm_session_ridge_path
+ * (b_path_out nl x (p+1), row k = [a0; b]; pred_out[k*n_eval + i]); rows past *nl_done_out are not written.
+ * dev_ratio_out[k] = 1 − ‖e‖²/‖y − ȳ‖², passes_out[k], nnz_out[k] (nl each) and nl_done_out may be NULL.
+ * Reaching max_passes at some λ still returns GBM_OK, and gbm_last_error() then holds a message starting
+ * "warning:" (it is "" after any other successful call of this function). Uses the training-set cache of
+ * gbm_session_ridge_path (a ridge path on the same rows is a cache hit and vice versa). Deterministic: two
+ * calls give the same bits. glmnet's first λ for this alpha is gbm_session_ridge_lambda_max · 1e-3/max(alpha, 1e-3).
+ */
+int gbm_session_enet_path(gbm_session* s, const int64_t* idx, int64_t n_train, const double* y, double alpha,
+                          const double* lambdas, int64_t nl, double tol, int64_t max_passes, double dev_max, double fdev,
+                          double* b_path_out /* nl x (p+1), as gbm_session_ridge_path */,
+                          const int64_t* idx_eval, int64_t n_eval, double* pred_out /* as ridge_path */,
+                          int64_t* nl_done_out, double* dev_ratio_out, int64_t* passes_out, int64_t* nnz_out);
 /* GRM builds and cache hits so far. */
 int gbm_session_stats(gbm_session* s, int64_t* grm_builds, int64_t* grm_hits);
 /* GWAS scan over all p loci on the rows idx[0..n_train) (reference gwasreml / gwasols, src/gwas.jl). For the
