@@ -52,6 +52,12 @@ int64_t knob_i64(const char* name, int64_t def);
 int launch_grm(const double* Zt, int64_t ldz, int64_t p, int64_t n, double* G, int64_t ldg,
                void* ws, int64_t ws_bytes, hipStream_t s, int accum = 0, int32_t* err_out = nullptr);
 bool grm_can_accumulate(int64_t n, int64_t p);
+// the GBLUP standardisation of fp64 locus rows (stats.hip; gbm_dev_standardize without its argument checks).
+// beside_tiles: the launch runs concurrently with the persistent GRM tile workgroups and takes a kernel that is
+// resident beside them (same bits), which exists where standardize_fits_beside_tiles(n)
+int launch_standardize_rows(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz, double* mean,
+                            double* sd, int32_t* keep, int64_t* q_dev, hipStream_t s, bool beside_tiles = false);
+bool standardize_fits_beside_tiles(int64_t n);
 int64_t grm_workspace_bytes(int64_t n, int64_t p);
 int launch_grm_export(const double* G, int64_t ldg, int64_t n, double inv_q, double* out, int64_t ldo, hipStream_t s);
 int launch_predict(const double* Xt, int64_t ldx, int64_t p, int64_t n, const double* b, int64_t ldb, int64_t nrhs,

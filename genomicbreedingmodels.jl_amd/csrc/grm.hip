@@ -22,7 +22,7 @@
 // loci-range sizes instead of the planner's), GBM_GRM_FUSED=1 (the slab reduce inside the persistent tile
 // kernel; same bits, opt-in: DESIGN.md §7, round 6), GBM_GRM_DIAG=0 (whole diagonal tiles in the quadrant
 // form instead of their 36 upper 16x16 blocks; same bits), GBM_GRM_DIAG_COST (the planner's cost of a
-// diagonal unit).
+// diagonal unit), GBM_GRM_STD_OVERLAP=0 (launch_standardize_grm_syrk standardises every row ahead of the tiles).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -278,6 +278,9 @@ struct SliceBounds {
   int32_t fuse = 0;
   // diag = 1 (GBM_GRM_DIAG): whole diagonal tiles compute only their 36 upper 16x16 blocks (diag_tile)
   int32_t diag = 0;
+  // the ranges [s0, s0 + cnt) a persistent launch draws from its queues (set by the launcher): all n of them,
+  // or range 0 and ranges 1 .. n − 1 in two launches (launch_standardize_grm_syrk)
+  int32_t s0 = 0, cnt = 0;
 };
 
 // Ragged last tile column of the GRM: when n = 128 (nt − 1) + r with small r, the last tile
@@ -561,13 +564,13 @@ syrk_kernel(const double* __restrict__ U, int64_t ldu, int64_t K, int64_t c0, in
         __syncthreads();
         const int64_t u = s_unit;
         __syncthreads();
-        if (u >= nq * sb.n) {
+        if (u >= nq * sb.cnt) {
           q = (q + 1) & 7;
           tries++;
           continue;
         }
-        const int sl = (int)(u / nq);
-        run_unit(sl, qt0 + (u - (int64_t)sl * nq));
+        const int r = (int)(u / nq);
+        run_unit(sb.s0 + r, qt0 + (u - (int64_t)r * nq));
       }
       return;
     } else {
@@ -1143,9 +1146,16 @@ static int aux_stream(hipStream_t caller, AuxStream& a, bool* usable) {
   return GBM_OK;
 }
 
-// workspace: [slabs or carry flags][edge partials][8 queue counters of the persistent launch, then (fused
-// reduce) one ticket counter per tile]
-static int64_t grm_counter_doubles(const GrmPlan& g) { return 4 + (g.sb.fuse ? (g.ntiles + 1) / 2 : 0); }
+// workspace: [slabs or carry flags][edge partials][the second launch's block][8 queue counters of the persistent
+// launch, then (fused reduce) one ticket counter per tile]. The second launch's block holds the 8 queue counters of
+// launch_standardize_grm_syrk's launch B, in plans that can take that path; it is one slab long, so that the
+// workspace stays a whole number of slabs plus the 32-byte counter block (part of the ABI's tested geometry).
+static int64_t grm_second_doubles(const GrmPlan& g) {
+  return (g.persist && !g.sb.fuse && g.sb.n >= 2) ? g.tile_elems : 0;
+}
+static int64_t grm_counter_doubles(const GrmPlan& g) {
+  return grm_second_doubles(g) + 4 + (g.sb.fuse ? (g.ntiles + 1) / 2 : 0);
+}
 int64_t grm_workspace_bytes(int64_t n, int64_t p) {
   const GrmPlan g = plan(n, p);
   return (g.main_doubles + g.edge_doubles + grm_counter_doubles(g)) * (int64_t)sizeof(double);
@@ -1157,6 +1167,45 @@ static int check_grm_args(const double* Zt, int64_t ldz, int64_t p, int64_t n, d
     return fail(GBM_E_ARG, "gbm_dev_grm: bad arguments (need ldz, ldg >= npad(n), both even)");
   if (((uintptr_t)Zt & 15) != 0 || ((uintptr_t)G & 15) != 0)
     return fail(GBM_E_ARG, "gbm_dev_grm: Zt and G must be 16-byte aligned");
+  return GBM_OK;
+}
+
+// The persistent tile kernel over the loci ranges [s0, s0 + cnt) of every tile; ctr: the launch's 8 queue
+// counters (then, fused, the tiles' ticket counters), zeroed by the caller.
+static int launch_persist(const GrmPlan& g, SliceBounds sb, int s0, int cnt, const double* Zt, int64_t ldz, int64_t p,
+                          int64_t lim, double* G, int64_t ldg, void* ws, int32_t* ctr, hipStream_t s) {
+  sb.s0 = s0;
+  sb.cnt = cnt;
+  const int64_t units = (int64_t)cnt * g.ntiles;
+  const unsigned pgrid = (unsigned)(units < resident_wgs() ? units : resident_wgs());
+  if (g.sb.fuse)
+    syrk_kernel<kPersistFused><<<pgrid, 256, 0, s>>>(Zt, ldz, p, 0, lim, G, ldg, (double*)ws, g.ntiles, sb, nullptr,
+                                                     nullptr, ctr, -1, TileOwner{});
+  else
+    syrk_kernel<kPersist><<<pgrid, 256, 0, s>>>(Zt, ldz, p, 0, lim, G, ldg, (double*)ws, g.ntiles, sb, nullptr,
+                                                nullptr, ctr, -1, TileOwner{});
+  GBM_LAUNCH_CHECK();
+  return GBM_OK;
+}
+
+// The ragged-column kernel on stream es and, when it runs beside the tiles, its reduce.
+static int launch_grm_edge(const GrmPlan& g, const double* Zt, int64_t ldz, int64_t p, int64_t n, double* G,
+                           int64_t ldg, void* ws, int accum, hipStream_t es) {
+  const unsigned eg = (unsigned)((int64_t)g.sb.erb * g.sb.es);
+  double* part = (double*)ws + g.sb.eslab_off;
+  switch (g.sb.et) {
+    case 1: grm_edge_kernel<1><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
+    case 2: grm_edge_kernel<2><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
+    case 3: grm_edge_kernel<3><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
+    default: grm_edge_kernel<4><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
+  }
+  GBM_LAUNCH_CHECK();
+  if (g.edge_concurrent) {
+    // the edge columns of G are disjoint from the tiles: sum their partials here, on the helper
+    // stream when there is one (launch_grm_reduce then skips them)
+    grm_edge_reduce_kernel<<<(unsigned)((n * g.sb.er + 255) / 256), 256, 0, es>>>(part, n, g.sb, G, ldg, accum);
+    GBM_LAUNCH_CHECK();
+  }
   return GBM_OK;
 }
 
@@ -1175,7 +1224,7 @@ int launch_grm_syrk(const double* Zt, int64_t ldz, int64_t p, int64_t n, double*
                                std::to_string(need) + ")");
   const unsigned grid = (unsigned)(g.sb.n * ((g.ntiles + 7) & ~(int64_t)7));
   if (g.sb.carry) GBM_HIP_TRY(hipMemsetAsync(ws, 0, (size_t)(g.ntiles + 1) * sizeof(int32_t), s));
-  int32_t* ctr = reinterpret_cast<int32_t*>((double*)ws + g.main_doubles + g.edge_doubles);
+  int32_t* ctr = reinterpret_cast<int32_t*>((double*)ws + g.main_doubles + g.edge_doubles + grm_second_doubles(g));
   const int64_t lim = g.sb.er > 0 ? g.sb.e0 : n;  // with an edge, the tiles cover [0, e0)^2 exactly
   // the ragged-column kernel beside the persistent tiles: forked (before the tile launch) onto
   // the device's helper stream; its workgroups fit in the registers the two tile workgroups of a
@@ -1194,41 +1243,75 @@ int launch_grm_syrk(const double* Zt, int64_t ldz, int64_t p, int64_t n, double*
   }
   if (g.persist) {
     GBM_HIP_TRY(hipMemsetAsync(ctr, 0, (size_t)(8 + (g.sb.fuse ? g.ntiles : 0)) * sizeof(int32_t), s));
-    const int64_t units = (int64_t)g.sb.n * g.ntiles;
-    const unsigned pgrid = (unsigned)(units < resident_wgs() ? units : resident_wgs());
-    if (g.sb.fuse)
-      syrk_kernel<kPersistFused><<<pgrid, 256, 0, s>>>(Zt, ldz, p, 0, lim, G, ldg, (double*)ws, g.ntiles, sb, nullptr,
-                                                       nullptr, ctr, -1, TileOwner{});
-    else
-      syrk_kernel<kPersist><<<pgrid, 256, 0, s>>>(Zt, ldz, p, 0, lim, G, ldg, (double*)ws, g.ntiles, sb, nullptr,
-                                                  nullptr, ctr, -1, TileOwner{});
+    rc = launch_persist(g, sb, 0, g.sb.n, Zt, ldz, p, lim, G, ldg, ws, ctr, s);
+    if (rc != GBM_OK) return rc;
   } else {
     syrk_kernel<kSplit><<<grid, 256, 0, s>>>(Zt, ldz, p, 0, lim, G, ldg, (double*)ws, g.ntiles, sb, nullptr, nullptr,
                                              nullptr, -1, TileOwner{});
-  }
-  GBM_LAUNCH_CHECK();
-  if (g.sb.er > 0) {
-    const hipStream_t es = ax ? ax->s : s;
-    const unsigned eg = (unsigned)((int64_t)g.sb.erb * g.sb.es);
-    double* part = (double*)ws + g.sb.eslab_off;
-    switch (g.sb.et) {
-      case 1: grm_edge_kernel<1><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
-      case 2: grm_edge_kernel<2><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
-      case 3: grm_edge_kernel<3><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
-      default: grm_edge_kernel<4><<<eg, 256, 0, es>>>(Zt, ldz, p, g.sb, part); break;
-    }
     GBM_LAUNCH_CHECK();
-    if (g.edge_concurrent) {
-      // the edge columns of G are disjoint from the tiles: sum their partials here, on the helper
-      // stream when there is one (launch_grm_reduce then skips them)
-      grm_edge_reduce_kernel<<<(unsigned)((n * g.sb.er + 255) / 256), 256, 0, es>>>(part, n, g.sb, G, ldg, accum);
-      GBM_LAUNCH_CHECK();
-    }
+  }
+  if (g.sb.er > 0) {
+    rc = launch_grm_edge(g, Zt, ldz, p, n, G, ldg, ws, accum, ax ? ax->s : s);
+    if (rc != GBM_OK) return rc;
     if (ax) {
       GBM_HIP_TRY(hipEventRecord(ax->join, ax->s));
       GBM_HIP_TRY(hipStreamWaitEvent(s, ax->join, 0));
     }
   }
+  return GBM_OK;
+}
+
+// The standardisation of the raw rows X into Zt and stage 1 of their GRM in one call: the same Z, mean, sd,
+// keep, q and slabs as launch_standardize_rows followed by launch_grm_syrk. Where the plan is the persistent
+// slab mode with S >= 2 ranges, the standardisation kernel fits beside the tile workgroups and the helper
+// stream is usable (GBM_GRM_STD_OVERLAP=0 forces the serial sequence), only the first range's h rows are
+// standardised ahead of the tiles:
+//   caller's stream: standardise rows [0, h), zero both counter blocks, fork, launch A (range 0), wait join
+//   helper stream:   wait fork, standardise rows [h, p), the edge kernel and its reduce (they read all of Z),
+//                    launch B (ranges 1 .. S − 1), join
+// Stream events do all the ordering. A and B are on different streams, so B's workgroups take the slots A's
+// leave as the range-0 queues run dry (the unit order of the single launch); each unit sums its own range in
+// the same order into the same slab, so G after the reduce has the same bits. Both standardise launches add
+// their kept rows into q (integer atomics), which the caller has zeroed.
+int launch_standardize_grm_syrk(const double* X, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz,
+                                double* mean, double* sd, int32_t* keep, int64_t* q, double* G, int64_t ldg, void* ws,
+                                int64_t ws_bytes, hipStream_t s) {
+  int rc = check_grm_args(Zt, ldz, p, n, G, ldg);
+  if (rc != GBM_OK) return rc;
+  if (!X || !mean || !sd || !keep || !q || ldx < n || (X == Zt && ldx != ldz))
+    return fail(GBM_E_ARG, "gbm_dev_standardize_grm_syrk: bad arguments");
+  const GrmPlan g = plan(n, p);
+  const int64_t h = g.sb.n >= 2 ? std::min<int64_t>(p, (int64_t)BK * g.sb.b[1]) : p;
+  AuxStream aux;
+  bool overlap = knob_i64("GBM_GRM_STD_OVERLAP", 1) != 0 && g.persist && !g.sb.fuse && g.sb.n >= 2 && h < p &&
+                 standardize_fits_beside_tiles(n);
+  if (overlap) {
+    rc = aux_stream(s, aux, &overlap);
+    if (rc != GBM_OK) return rc;
+  }
+  if (!overlap) {
+    rc = launch_standardize_rows(X, ldx, p, n, Zt, ldz, mean, sd, keep, q, s);
+    if (rc != GBM_OK) return rc;
+    return launch_grm_syrk(Zt, ldz, p, n, G, ldg, ws, ws_bytes, s);
+  }
+  const int64_t need = (g.main_doubles + g.edge_doubles + grm_counter_doubles(g)) * (int64_t)sizeof(double);
+  if (!ws || ws_bytes < need)
+    return fail(GBM_E_ARG, "gbm_dev_standardize_grm_syrk: workspace too small (" + std::to_string(ws_bytes) + " < " +
+                               std::to_string(need) + ")");
+  // B's 8 counters end the second launch's block, right ahead of A's: one memset
+  int32_t* ctr = reinterpret_cast<int32_t*>((double*)ws + g.main_doubles + g.edge_doubles + grm_second_doubles(g)) - 8;
+  const int64_t lim = g.sb.er > 0 ? g.sb.e0 : n;
+  GBM_TRY(launch_standardize_rows(X, ldx, h, n, Zt, ldz, mean, sd, keep, q, s));
+  GBM_HIP_TRY(hipMemsetAsync(ctr, 0, 16 * sizeof(int32_t), s));
+  GBM_HIP_TRY(hipEventRecord(aux.fork, s));
+  GBM_HIP_TRY(hipStreamWaitEvent(aux.s, aux.fork, 0));
+  GBM_TRY(launch_persist(g, g.sb, 0, 1, Zt, ldz, p, lim, G, ldg, ws, ctr + 8, s));
+  GBM_TRY(launch_standardize_rows(X + h * ldx, ldx, p - h, n, Zt + h * ldz, ldz, mean + h, sd + h, keep + h, q, aux.s,
+                                  true));
+  if (g.sb.er > 0) GBM_TRY(launch_grm_edge(g, Zt, ldz, p, n, G, ldg, ws, 0, aux.s));
+  GBM_TRY(launch_persist(g, g.sb, 1, g.sb.n - 1, Zt, ldz, p, lim, G, ldg, ws, ctr, aux.s));
+  GBM_HIP_TRY(hipEventRecord(aux.join, aux.s));
+  GBM_HIP_TRY(hipStreamWaitEvent(s, aux.join, 0));
   return GBM_OK;
 }
 
@@ -1341,6 +1424,13 @@ extern "C" int gbm_dev_grm_accumulate(const double* Zt, int64_t ldz, int64_t p, 
 extern "C" int gbm_dev_grm_syrk(const double* Zt, int64_t ldz, int64_t p, int64_t n, double* G, int64_t ldg,
                                 void* workspace, int64_t ws_bytes, void* stream) {
   return gbm::launch_grm_syrk(Zt, ldz, p, n, G, ldg, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int gbm_dev_standardize_grm_syrk(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz,
+                                            double* mean, double* sd, int32_t* keep, int64_t* q_dev, double* G,
+                                            int64_t ldg, void* workspace, int64_t ws_bytes, void* stream) {
+  return gbm::launch_standardize_grm_syrk(Xt, ldx, p, n, Zt, ldz, mean, sd, keep, q_dev, G, ldg, workspace, ws_bytes,
+                                          (hipStream_t)stream);
 }
 
 extern "C" int gbm_dev_grm_reduce(int64_t n, int64_t p, double* G, int64_t ldg, const void* workspace, void* stream) {

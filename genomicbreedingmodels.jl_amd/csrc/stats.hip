@@ -321,6 +321,27 @@ static int launch_standardize(const T* Xt, int64_t ldx, int64_t p, const int32_t
 }
 
 namespace gbm {
+// The standardisation of fp64 rows beside the persistent GRM tile workgroups (launch_standardize_grm_syrk, grm.hip):
+// a CU's two tile workgroups leave 128 VGPRs per lane and 27 KB of LDS, and the kernel the dispatch above picks for
+// 4096 < n <= 8192 (NPT = 32: 184 VGPRs) would not be resident there. For such launches (beside_tiles) n up to 5120
+// runs at NPT = 20 (121 VGPRs; NPT <= 16 takes at most 101, NPT = 24 would take 141; all 32 B of LDS). Thread t
+// adds x[256 k + t] for ascending k whatever the NPT, and the terms a smaller NPT drops are + 0.0, so mean, sd and Z
+// are the same bits (but the sign of a row sum whose terms are all −0.0). Launches that run alone keep NPT = 32: at
+// C2, NPT = 20 alone measured 0.64 ms in one process and 0.76 ms in another against a steady 0.67 ms.
+bool standardize_fits_beside_tiles(int64_t n) { return n <= 256 * 20; }
+
+int launch_standardize_rows(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz, double* mean,
+                            double* sd, int32_t* keep, int64_t* q_dev, hipStream_t s, bool beside_tiles) {
+  if (p == 0) return GBM_OK;
+  if (beside_tiles && n > 256 * 16 && n <= 256 * 20) {
+    standardize_kernel<256, 20, false, double><<<(unsigned)(p < 256 * 16 ? p : 256 * 16), 256, 0, s>>>(
+        Xt, ldx, p, nullptr, n, Zt, ldz, mean, sd, keep, reinterpret_cast<unsigned long long*>(q_dev), 0, 1.0);
+    GBM_LAUNCH_CHECK();
+    return GBM_OK;
+  }
+  return launch_standardize<false>(Xt, ldx, p, nullptr, n, Zt, ldz, mean, sd, keep, q_dev, 0, s);
+}
+
 int launch_center_columns(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz, double* mean,
                           double* sd, int32_t* keep, int64_t* q_dev, hipStream_t s) {
   if (p == 0) return GBM_OK;

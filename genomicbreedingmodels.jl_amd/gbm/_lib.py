@@ -46,7 +46,7 @@ EXPORTS = (
     "gbm_gblup_fit_ex", "gbm_gblup_fit_reml_ex", "gbm_gblup_fit_dosage_i8_ex", "gbm_gblup_fit_synthetic_ex",
     "gbm_session_set_grm_mode", "gbm_session_grm_used", "gbm_debug_rccl_calls", "gbm_debug_xg_choose", "gbm_debug_chol_flow_order",
     "gbm_debug_chol_flow_order_check", "gbm_debug_chol_flow_order_size", "gbm_dev_grm_exact_status", "gbm_debug_set",
-    "gbm_dev_whiten_rows", "gbm_session_gwas", "gbm_session_enet_path",
+    "gbm_dev_whiten_rows", "gbm_session_gwas", "gbm_session_enet_path", "gbm_dev_standardize_grm_syrk",
 )
 
 GBM_GRM_DEFAULT, GBM_GRM_FP64, GBM_GRM_EXACT, GBM_GRM_AUTO, GBM_GRM_DROPIN = -1, 0, 1, 2, 3
@@ -169,6 +169,8 @@ def _declare(lib):
     for f in ("gbm_dev_grm", "gbm_dev_grm_syrk", "gbm_dev_grm_accumulate"):
         getattr(lib, f).restype = I32
         getattr(lib, f).argtypes = [P, I64, I64, I64, P, I64, P, I64, P]
+    lib.gbm_dev_standardize_grm_syrk.restype = I32
+    lib.gbm_dev_standardize_grm_syrk.argtypes = [P, I64, I64, I64, P, I64, P, P, P, P, P, I64, P, I64, P]
     lib.gbm_dev_grm_reduce.restype = I32
     lib.gbm_dev_grm_reduce.argtypes = [I64, I64, P, I64, P, P]
     lib.gbm_dev_grm_slices.restype = I32

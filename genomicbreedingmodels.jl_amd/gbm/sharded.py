@@ -285,6 +285,22 @@ def assemble_b_hat(mu, msum, B_shards, p_total):
     return b_hat
 
 
+def _written_by_standardize(name):
+    """A HipShardStages buffer the standardisation writes: reading it runs a standardisation that standardize()
+    left to grm_syrk() first."""
+    attr = "_" + name
+
+    def get(self):
+        if self._std_pending:
+            self._standardize_now()
+        return getattr(self, attr)
+
+    def put(self, value):
+        setattr(self, attr, value)
+
+    return property(get, put)
+
+
 class HipShardStages:
     """Device-resident buffers of one shard (torch-allocated HBM) driven through libgbm's
     stream-ordered C ABI on torch's current stream."""
@@ -359,13 +375,36 @@ class HipShardStages:
         self.Y[:, :self.n].copy_(self.torch.from_numpy(np.ascontiguousarray(Y.T)))
 
     # ---- stages ---------------------------------------------------------------------------
+    # standardize() zeroes q and leaves the standardisation to grm_syrk(), which runs both through
+    # gbm_dev_standardize_grm_syrk (the rows behind the first loci range are standardised beside that range's
+    # tiles). Z, mean, sd, keep and q are properties: reading one between the two calls runs the deferred
+    # standardisation at once (gbm_dev_standardize), and grm_syrk() is then the GRM alone, as it is when called
+    # again without a standardize().
+    _std_pending = False
+    Z = _written_by_standardize("Z")
+    mean = _written_by_standardize("mean")
+    sd = _written_by_standardize("sd")
+    keep = _written_by_standardize("keep")
+    q = _written_by_standardize("q")
+
     def standardize(self):
-        self.q.zero_()
-        _lib.check(self.lib.gbm_dev_standardize(self._p(self.X), self.npad, self.p, self.n, self._p(self.Z), self.npad,
-                                                self._p(self.mean), self._p(self.sd), self._p(self.keep),
-                                                self._p(self.q), self._stream()), "standardize")
+        self._q.zero_()
+        self._std_pending = True
+
+    def _standardize_now(self):
+        self._std_pending = False
+        _lib.check(self.lib.gbm_dev_standardize(self._p(self.X), self.npad, self.p, self.n, self._p(self._Z), self.npad,
+                                                self._p(self._mean), self._p(self._sd), self._p(self._keep),
+                                                self._p(self._q), self._stream()), "standardize")
 
     def grm_syrk(self):
+        if self._std_pending:
+            self._std_pending = False
+            _lib.check(self.lib.gbm_dev_standardize_grm_syrk(
+                self._p(self.X), self.npad, self.p, self.n, self._p(self._Z), self.npad, self._p(self._mean),
+                self._p(self._sd), self._p(self._keep), self._p(self._q), self._p(self.G), self.gdim,
+                self._p(self.ws_grm), self.ws_grm_bytes, self._stream()), "standardize_grm_syrk")
+            return
         _lib.check(self.lib.gbm_dev_grm_syrk(self._p(self.Z), self.npad, self.p, self.n, self._p(self.G), self.gdim,
                                              self._p(self.ws_grm), self.ws_grm_bytes, self._stream()), "grm_syrk")
 

@@ -282,6 +282,14 @@ int gbm_dev_grm_accumulate(const double* Zt, int64_t ldz, int64_t p, int64_t n, 
 int gbm_dev_grm_syrk(const double* Zt, int64_t ldz, int64_t p, int64_t n, double* G, int64_t ldg,
                      void* workspace, int64_t ws_bytes, void* stream);
 int gbm_dev_grm_reduce(int64_t n, int64_t p, double* G, int64_t ldg, const void* workspace, void* stream);
+/* gbm_dev_standardize followed by gbm_dev_grm_syrk in one call, with the same bits in Zt, mean, sd, keep,
+ * *q_dev (caller zeroes it) and, after gbm_dev_grm_reduce, G. Where the plan has several loci ranges and the
+ * standardisation kernel fits beside the GRM tile workgroups (n <= 5120), only the first range's rows are
+ * standardised ahead of the tiles; the rest are standardised on a helper stream beside the first range's
+ * tiles. On return the caller's stream is ordered after all of it. GBM_GRM_STD_OVERLAP=0: always serial. */
+int gbm_dev_standardize_grm_syrk(const double* Xt, int64_t ldx, int64_t p, int64_t n, double* Zt, int64_t ldz,
+                                 double* mean, double* sd, int32_t* keep, int64_t* q_dev, double* G, int64_t ldg,
+                                 void* workspace, int64_t ws_bytes, void* stream);
 /* The upper 128x128 tiles of G as one contiguous array (packed size in doubles; pack; unpack):
  * half the bytes of G's npad x gdim rows, the form the multi-GPU partial-GRM all-reduce moves. */
 int64_t gbm_dev_grm_packed_size(int64_t n);

@@ -43,6 +43,13 @@ def main(root):
     syrk = [v for k, v in out["kernels"].items() if "syrk_kernel<2>" in k or "syrk_kernel<1>" in k]
     edge = [v for k, v in out["kernels"].items() if "grm_edge_kernel" in k]
     if syrk:
+        # a step's tiles may come as two launches (range 0, then the other ranges: launch_standardize_grm_syrk);
+        # "per launch" below means per GRM, i.e. per slab reduce
+        reduces = [v for k, v in out["kernels"].items() if "grm_slab_reduce_kernel" in k]
+        per_grm = syrk[0]["launches"] // reduces[0]["launches"] if reduces and reduces[0]["launches"] else 1
+        out["syrk_launches_per_grm"] = max(per_grm, 1)
+        if per_grm > 1 and syrk[0]["hbm_bytes_per_launch"]:
+            syrk[0] = dict(syrk[0], hbm_bytes_per_launch=syrk[0]["hbm_bytes_per_launch"] * per_grm)
         out["syrk_bytes_per_launch"] = syrk[0]["hbm_bytes_per_launch"]
         out["edge_bytes_per_launch"] = edge[0]["hbm_bytes_per_launch"] if edge else 0
         out["hbm_bytes_per_launch"] = (syrk[0]["hbm_bytes_per_launch"] or 0) + (out["edge_bytes_per_launch"] or 0)
