@@ -147,6 +147,35 @@ int launch_enet_pass(const double* Za, int64_t lda, int64_t n, int64_t A, const 
                      double* blkmax, double* e, double* red, hipStream_t s);
 int launch_enet_norm(const double* e, int64_t n, double* red, hipStream_t s);
 
+// Block eigensolver on the symmetric K (pcs.hip; driver: gbm_session_pcs). Vector blocks are kPcsBlock x ld
+// row-major with zero padding columns; every reduction runs in a fixed order. The symmetric fill and the block
+// product are the ABI entries gbm_dev_grm_symmetrize / gbm_dev_rows_times_sym.
+constexpr int kPcsBlock = 32;
+int64_t rows_times_sym_splits(int64_t n);
+// m_j = Σ_i K_ij / n and the ddof-1 column standard deviation s_j (two passes); 0 on the padding
+int launch_pcs_colstats(const double* K, int64_t ldk, int64_t n, double* m, double* s, hipStream_t st);
+// rows_out[i] = Σ_j (K̃_ij − mean_j K̃_ij)², K̃ = (K − 1mᵀ)D⁻¹: row i's share of the reference operator's trace
+int launch_pcs_rowtrace(const double* K, int64_t ldk, int64_t n, const double* m, const double* s, double* rows_out,
+                        hipStream_t st);
+int launch_pcs_sum(const double* x, int64_t stride, int64_t n, double* out, hipStream_t st);  // out[0] = Σ x[i·stride]
+// the reference operator around its two block products: Wt = D⁻¹H D⁻¹(P − c mᵀ) with c = Qt·1, then Yt −= 1(mᵀW)
+int launch_pcs_ref_mid(const double* Qt, int64_t ldq, const double* P, int64_t ldp, int64_t n, const double* m,
+                       const double* s, double* Wt, int64_t ldw, hipStream_t st);
+int launch_pcs_ref_post(const double* Wt, int64_t ldw, int64_t n, const double* m, double* Yt, int64_t ldy,
+                        hipStream_t st);
+// out[0] = A Bᵀ and, with npairs = 2, out[1] = B Bᵀ (32 x 32 row-major each); part: pcs_gram_workspace(n) bytes
+int64_t pcs_gram_workspace(int64_t n);
+int launch_pcs_gram(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t n, int npairs, double* part,
+                    double* out, hipStream_t st);
+// Out[v, :] = Σ_u Mx[v][u] In[u, :], v < nout (Mx 32 x 32 row-major, device)
+int launch_pcs_transform(const double* Mx, const double* In, int64_t ldi, int64_t n, int nout, double* Out, int64_t ldo,
+                         hipStream_t st);
+// part[c·16 + i] = chunk c's share of ‖s_iᵀY − θ_i s_iᵀQ‖², i < k <= 16 (St: rows s_i, then θ at St + 1024)
+int64_t pcs_resid_chunks(int64_t n);
+int launch_pcs_resid(const double* St, const double* Q, int64_t ldq, const double* Y, int64_t ldy, int64_t n, int k,
+                     double* part, hipStream_t st);
+int launch_pcs_start(double* Q, int64_t ldq, int64_t n, uint64_t seed, hipStream_t st);
+
 // REML choice of λ (session.cpp; reference loglikreml src/gwas.jl:450-483 with X = 1)
 struct RemlEval {
   double g, s2u, s2e;  // objective, σ²_u, σ²_e at one λ (σ²_u profiled inside the box [eps, 1]²)

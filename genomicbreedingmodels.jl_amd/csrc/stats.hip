@@ -2,18 +2,12 @@
 // standardisation of reference src/gwas.jl:112-115,127-130 (HBM-bound; one pass over X).
 #include <type_traits>
 
+#include "counter_hash.h"
 #include "gbm_internal.h"
 
 namespace gbm {
 
-// ---- counter-based genotype generator (bit-identical to oracle/gbm_oracle.c) -------------
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
+// ---- counter-based genotype generator (bit-identical to oracle/gbm_oracle.c; mix64: counter_hash.h) -------------
 // One workgroup strip of 1024 columns of one locus row per blockIdx.x; rows grid-strided on y.
 __global__ void __launch_bounds__(256) synth_kernel(double* __restrict__ Xt, int64_t ldx, int64_t p,
                                                     int64_t n, uint64_t seed, int64_t j0) {

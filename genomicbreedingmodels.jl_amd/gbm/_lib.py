@@ -47,9 +47,13 @@ EXPORTS = (
     "gbm_session_set_grm_mode", "gbm_session_grm_used", "gbm_debug_rccl_calls", "gbm_debug_xg_choose", "gbm_debug_chol_flow_order",
     "gbm_debug_chol_flow_order_check", "gbm_debug_chol_flow_order_size", "gbm_dev_grm_exact_status", "gbm_debug_set",
     "gbm_dev_whiten_rows", "gbm_session_gwas", "gbm_session_enet_path", "gbm_dev_standardize_grm_syrk",
+    "gbm_dev_grm_symmetrize", "gbm_dev_rows_times_sym", "gbm_dev_rows_times_sym_workspace", "gbm_session_pcs",
+    "gbm_debug_sym_eig",
 )
 
 GBM_GRM_DEFAULT, GBM_GRM_FP64, GBM_GRM_EXACT, GBM_GRM_AUTO, GBM_GRM_DROPIN = -1, 0, 1, 2, 3
+GBM_PCS_GRM, GBM_PCS_REFERENCE = 0, 1
+PCS_KINDS = {"grm": GBM_PCS_GRM, "reference": GBM_PCS_REFERENCE}
 GRM_MODES = {None: GBM_GRM_DEFAULT, "default": GBM_GRM_DEFAULT, "fp64": GBM_GRM_FP64, "exact": GBM_GRM_EXACT,
              "auto": GBM_GRM_AUTO, "dropin": GBM_GRM_DROPIN}
 
@@ -247,6 +251,16 @@ def _declare(lib):
     lib.gbm_dev_whiten_rows.argtypes = [P, I64, I64, P, P, I64, I64, P]
     lib.gbm_session_gwas.restype = I32
     lib.gbm_session_gwas.argtypes = [P, P, I64, P, P, I64, I64, I32, D, D, P, P, P, P]
+    lib.gbm_dev_grm_symmetrize.restype = I32
+    lib.gbm_dev_grm_symmetrize.argtypes = [P, I64, I64, D, P, I64, P]
+    lib.gbm_dev_rows_times_sym_workspace.restype = I64
+    lib.gbm_dev_rows_times_sym_workspace.argtypes = [I64, I64]
+    lib.gbm_dev_rows_times_sym.restype = I32
+    lib.gbm_dev_rows_times_sym.argtypes = [P, I64, I64, P, I64, I64, P, I64, P, I64, P]
+    lib.gbm_session_pcs.restype = I32
+    lib.gbm_session_pcs.argtypes = [P, P, I64, I32, I64, D, I64, P, P, P, P, P]
+    lib.gbm_debug_sym_eig.restype = I32
+    lib.gbm_debug_sym_eig.argtypes = [P, I32, P, P]
     lib.gbm_debug_set.restype = I32
     lib.gbm_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     return lib
@@ -302,9 +316,9 @@ def check(rc: int, what: str):
     if rc == GBM_OK:
         return
     msg = f"{what}: {last_error()} (code {rc})"
-    if rc == GBM_E_ARG:
-        raise ArgumentError(msg)
-    raise GBMError(msg)
+    err = ArgumentError(msg) if rc == GBM_E_ARG else GBMError(msg)
+    err.code = rc  # the library's return code, for callers that handle one outcome (gwasols: GBM_E_DATA of pcs)
+    raise err
 
 
 def device_count() -> int:

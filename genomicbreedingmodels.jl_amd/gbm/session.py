@@ -7,11 +7,12 @@ src/cross_validation.jl:159-186 refits everything per fold)."""
 from __future__ import annotations
 
 import ctypes
+import warnings
 
 import numpy as np
 
 from . import _lib
-from ._lib import ArgumentError
+from ._lib import ArgumentError, GBMError
 
 
 def _idx(idx) -> np.ndarray:
@@ -155,9 +156,44 @@ class GenotypeSession:
         _lib.check(rc, "gbm_session_reml")
         return {"lambda": float(v[0]), "sigma2_e": float(v[1]), "sigma2_u": float(v[2]), "objective": float(v[3])}
 
-    def gwas(self, idx, y, covariates=None, model: str = "mlm", sigma2=None) -> dict:
+    def pcs(self, idx, k: int = 1, kind: str = "grm", tol: float = 1e-10, max_iter: int = 1000) -> dict:
+        """Leading ``k`` (<= 16) eigenpairs of the relationship matrix of rows ``idx`` (>= 64 of them), by block
+        subspace iteration on the cached GRM (gbm_session_pcs). ``kind``: "grm" (K = ZZᵀ/q, the matrix of
+        :meth:`gwas`) or "reference" (the PCA of the column-standardised K that reference gwasols takes its PC1
+        from, src/gwas.jl:130, 234; :func:`gbm.gwas.pc1_of_grm`). Stops when every relative Ritz residual
+        ‖Mv − θv‖/θ₁ is below ``tol``, or after ``max_iter`` iterations (then ``converged`` is False and a
+        warning is issued). Returns dict(vectors (n_train, k) [unit columns, largest component positive], values
+        (k,) descending, trace, resid (k,), iters, converged)."""
+        idx = _idx(idx)
+        try:
+            kd = _lib.PCS_KINDS[kind]
+        except (KeyError, TypeError):
+            raise ArgumentError(f"kind must be 'grm' or 'reference', got {kind!r}") from None
+        k = int(k)
+        if not 1 <= k <= 16:
+            raise ArgumentError("k must be in [1, 16]")
+        vec = np.zeros((idx.size, k), order="F")
+        val, res = np.zeros(k), np.zeros(k)
+        tr = np.zeros(1)
+        it = np.zeros(1, dtype=np.int64)
+        rc = self.lib.gbm_session_pcs(self._h, _lib.ptr(idx), idx.size, kd, k, float(tol), int(max_iter), _lib.ptr(vec),
+                                      _lib.ptr(val), _lib.ptr(tr), _lib.ptr(res), _lib.ptr(it))
+        _lib.check(rc, "gbm_session_pcs")
+        msg = _lib.last_error()
+        converged = not msg.startswith("warning:")
+        if not converged:
+            warnings.warn(msg, RuntimeWarning, stacklevel=2)
+        return {"vectors": vec, "values": val, "trace": float(tr[0]), "resid": res, "iters": int(it[0]),
+                "converged": converged}
+
+    def gwas(self, idx, y, covariates=None, model: str = "mlm", sigma2=None, n_pcs: int = 0, pcs_tol: float = 1e-10,
+             pcs_max_iter: int = 1000) -> dict:
         """GWAS scan over all p loci on rows ``idx`` (gbm_session_gwas; reference gwasreml / gwasols,
         src/gwas.jl:591-599, 241-245). ``covariates``: (n_train,) or (n_train, kc <= 7) beside the intercept.
+        ``n_pcs`` > 0 appends that many leading principal components of K = ZZᵀ/q (:meth:`pcs`, kind "grm") to
+        the covariates (kc + n_pcs <= 7), computed with ``pcs_tol`` and ``pcs_max_iter``; the scan never runs on
+        unconverged components: GBMError is raised when they do not converge, as it is by :meth:`pcs` itself when
+        the block loses rank (fewer than 32 eigenvalues of K above rounding).
         ``model``: "mlm" (V = σ²_u ZZᵀ/q + σ²_e I on the cached GRM factor) or "ols" (V = I). ``sigma2``:
         (σ²_e, σ²_u) for "mlm", or None to estimate them once by the null-model REML of :meth:`reml`.
         Returns dict(z (p,), b (p,), sigma2_e, sigma2_u, tested); untested loci (not polymorphic in the rows, or in
@@ -180,12 +216,27 @@ class GenotypeSession:
                 raise ArgumentError("covariates must have one row per training index")
             C = np.asfortranarray(C)
             kc = C.shape[1]
+        n_pcs = int(n_pcs)
+        if n_pcs < 0 or (n_pcs > 0 and kc + n_pcs > 7):  # without PCs the library checks kc as before
+            raise ArgumentError(f"n_pcs must be >= 0 with at most 7 covariates in all (got {kc} covariates + "
+                                f"{n_pcs} principal components)")
         if sigma2 is None:
             s2e = s2u = float("nan")
         else:
             s2e, s2u = (float(v) for v in sigma2)
             if m == 0 and (np.isnan(s2e) or np.isnan(s2u)):
                 raise ArgumentError("sigma2 must be a pair of positive numbers (None: estimate by REML)")
+        if n_pcs > 0:
+            with warnings.catch_warnings():  # not converged is an error here, not a warning
+                warnings.simplefilter("ignore", RuntimeWarning)
+                rp = self.pcs(idx, n_pcs, kind="grm", tol=pcs_tol, max_iter=pcs_max_iter)
+            if not rp["converged"]:
+                raise GBMError(f"gwas: the {n_pcs} principal components did not converge in {rp['iters']} iterations "
+                               f"(largest relative residual {rp['resid'].max():.3g} against pcs_tol {pcs_tol:.3g}); "
+                               "raise pcs_max_iter or pcs_tol, or pass covariates of your own")
+            pcs = rp["vectors"]
+            C = np.asfortranarray(pcs if C is None else np.column_stack([C, pcs]))
+            kc += n_pcs
         z = np.zeros(self.p)
         b = np.zeros(self.p)
         used = np.zeros(2)

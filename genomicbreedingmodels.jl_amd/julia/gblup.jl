@@ -129,9 +129,34 @@ end
 # Differences from the reference loops, stated in include/gbm.h: the variance components are estimated once
 # under the null model (not per marker), K = ZZᵀ/q (not the column-standardised GRM), and the mixed model
 # runs on that simple GRM only (GRM_type = "ploidy-aware" is refused by gwasreml_gpu).
-function gbm_gwas_scan(G::Matrix{Float64}, y::Vector{Float64}, C::Matrix{Float64}, model::Integer; device::Integer = 0)
+# Leading k eigenpairs of the relationship matrix of the rows idx (0-based) of the session h (gbm_session_pcs):
+# kind 0 = K = ZZᵀ/q, kind 1 = the PCA of the column-standardised K that gwasols takes PC1 from (src/gwas.jl:130,234).
+# data_error = :nothing returns nothing instead of throwing when the library reports GBM_E_DATA (-7: the block lost
+# rank, i.e. fewer than 32 eigenvalues above rounding, or a column of K without variance), for callers with a host path.
+function gbm_session_pcs(h::Ptr{Cvoid}, idx::Vector{Int64}, k::Integer; kind::Integer = 0, tol::Float64 = 1e-10,
+                         max_iter::Integer = 1000, data_error::Symbol = :throw)
+    n = length(idx)
+    vectors = zeros(n, k)
+    values = zeros(k)
+    resid = zeros(k)
+    tr = zeros(1)
+    iters = zeros(Int64, 1)
+    rc = ccall((:gbm_session_pcs, LIBGBM), Cint,
+               (Ptr{Cvoid}, Ptr{Int64}, Int64, Cint, Int64, Float64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Int64}),
+               h, idx, n, kind, k, tol, max_iter, vectors, values, tr, resid, iters)
+    rc == -7 && data_error == :nothing && return nothing
+    gbm_check(rc, "pcs")
+    converged = !startswith(gbm_last_error(), "warning:")
+    (vectors = vectors, values = values, trace = tr[1], resid = resid, iters = iters[1], converged = converged)
+end
+
+# pc1 = :device: the scan's covariate is PC1 of the session's own cached GRM (kind 1, tol 1e-12; C is ignored); the
+# result's pc1_found says whether the iteration converged (otherwise, and when the library reports a data error such
+# as a block that lost rank, no scan was run and the caller falls back).
+function gbm_gwas_scan(G::Matrix{Float64}, y::Vector{Float64}, C::Matrix{Float64}, model::Integer; device::Integer = 0,
+                       pc1::Symbol = :given)
     n, p = size(G)
-    kc = size(C, 2)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     gbm_check(ccall((:gbm_session_create, LIBGBM), Cint,
                     (Ptr{Float64}, Int64, Int64, Int64, Cint, Ptr{Ptr{Cvoid}}), G, n, p, n, device, h),
@@ -141,16 +166,25 @@ function gbm_gwas_scan(G::Matrix{Float64}, y::Vector{Float64}, C::Matrix{Float64
     σ2 = zeros(2)
     tested = zeros(Int64, 1)
     idx = collect(Int64, 0:(n-1))
+    found = true
     try
-        gbm_check(ccall((:gbm_session_gwas, LIBGBM), Cint,
-                        (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Cint, Float64, Float64,
-                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
-                        h[], idx, n, y, kc > 0 ? C : Ptr{Float64}(C_NULL), n, kc, model, NaN, NaN, z, b, σ2, tested),
-                  "gwas")
+        if pc1 == :device
+            r = gbm_session_pcs(h[], idx, 1; kind = 1, tol = 1e-12, data_error = :nothing)
+            found = !isnothing(r) && r.converged
+            found && (C = r.vectors)
+        end
+        kc = size(C, 2)
+        if found
+            gbm_check(ccall((:gbm_session_gwas, LIBGBM), Cint,
+                            (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Cint, Float64, Float64,
+                             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                            h[], idx, n, y, kc > 0 ? C : Ptr{Float64}(C_NULL), n, kc, model, NaN, NaN, z, b, σ2, tested),
+                      "gwas")
+        end
     finally
         ccall((:gbm_session_destroy, LIBGBM), Cvoid, (Ptr{Cvoid},), h[])
     end
-    (z = z, b = b, σ2_e = σ2[1], σ2_u = σ2[2], tested = tested[1])
+    (z = z, b = b, σ2_e = σ2[1], σ2_u = σ2[2], tested = tested[1], pc1_found = found)
 end
 
 """
@@ -174,18 +208,30 @@ function gwasreml_gpu(; genomes::Genomes, phenomes::Phenomes, idx_entries = noth
 end
 
 """
-    gwasols_gpu(; genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, GRM_type="simple", verbose=false)::Fit
+    gwasols_gpu(; genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, GRM_type="simple", pc="auto", verbose=false)::Fit
 
-`gwasols` (src/gwas.jl:146-260) with the marker loop on the GPU; PC1 of the (standardised) GRM is computed on the
+`gwasols` (src/gwas.jl:146-260) with the marker loop on the GPU. `pc = "auto"` with the simple GRM: PC1 comes from the
+scan's own session on the device (`gbm_session_pcs`, the reference's PCA of the column-standardised GRM; one GRM
+build, no n² transfer), and the host path is the fallback when the iteration does not converge, when the library
+reports a data error (the block lost rank: fewer than about 31 polymorphic loci-alleles) or there are fewer than 64
+entries. `pc = "host"`, and the ploidy-aware GRM always: PC1 of the GRM `gwasprep` returns, computed on the
 host exactly as the reference does (src/gwas.jl:234).
 """
 function gwasols_gpu(; genomes::Genomes, phenomes::Phenomes, idx_entries = nothing, idx_loci_alleles = nothing,
-                     idx_trait::Int64 = 1, GRM_type::String = "simple", verbose::Bool = false)::Fit
+                     idx_trait::Int64 = 1, GRM_type::String = "simple", pc::String = "auto", verbose::Bool = false)::Fit
+    pc in ("auto", "host") || throw(ArgumentError("Unrecognised `pc`. Please select from: auto, host"))
     G, y, GRM, fit = gwasprep(genomes = genomes, phenomes = phenomes, idx_entries = idx_entries,
                               idx_loci_alleles = idx_loci_alleles, idx_trait = idx_trait, GRM_type = GRM_type,
                               standardise = true, verbose = false)
-    E = MultivariateStats.fit(PCA, GRM; maxoutdim = 1)
-    r = gbm_gwas_scan(G, y, reshape(E.proj[:, 1], :, 1), 1)
+    r = nothing
+    if pc == "auto" && GRM_type == "simple" && size(G, 1) >= 64
+        r = gbm_gwas_scan(G, y, zeros(size(G, 1), 0), 1; pc1 = :device)
+        r.pc1_found || (r = nothing)
+    end
+    if isnothing(r)
+        E = MultivariateStats.fit(PCA, GRM; maxoutdim = 1)
+        r = gbm_gwas_scan(G, y, reshape(E.proj[:, 1], :, 1), 1)
+    end
     fit.model = "GWAS_OLS"
     fit.b_hat = r.z
     verbose && println("gwasols_gpu: tested=$(r.tested)")

@@ -412,6 +412,24 @@ int gbm_dev_gblup_terms(const double* G, int64_t ldg, int64_t n, int64_t nrhs, c
 int gbm_dev_whiten_rows(const double* G, int64_t ldg, int64_t n, const void* solve_workspace, double* R,
                         int64_t ldr, int64_t rows, void* stream);
 
+/* Symmetric fill of a GRM: K (npad x ldk row-major, out of place, ldk >= gbm_dev_npad(n) even, 16-byte aligned) gets
+ * scale·G in both triangles, read only from the elements gbm_dev_grm / gbm_dev_grm_exact_i8 define: the 128x128
+ * tiles with tile-row <= tile-column and, inside a diagonal tile, the 16x16 blocks with block-row <= block-column
+ * (the row <= column half of the diagonal blocks). Everything else of G is never read; rows and columns [n, npad)
+ * of K are zeros whatever G's padding holds; K[i, j] and K[j, i] are the same bits. ldg >= gbm_dev_npad(n). */
+int gbm_dev_grm_symmetrize(const double* G, int64_t ldg, int64_t n, double scale, double* K, int64_t ldk,
+                           void* stream);
+
+/* Skinny product Yt = Qt·K with the symmetric K of gbm_dev_grm_symmetrize (zero padding). Qt, Yt: rows x ld
+ * row-major vector blocks stored like locus rows (individuals contiguous, ld >= gbm_dev_npad(n) even, 16-byte
+ * aligned, padding columns zero); rows = 16, 32, 48 or 64. fp64 MFMA, HBM-bound on K: the individual range is split
+ * over workgroups (a count that depends on n alone) and the partial sums are added in a fixed order, so two calls
+ * give the same bits and a row's result does not depend on the other rows of the call. workspace:
+ * gbm_dev_rows_times_sym_workspace(n, rows) bytes, 16-byte aligned. */
+int64_t gbm_dev_rows_times_sym_workspace(int64_t n, int64_t rows);
+int gbm_dev_rows_times_sym(const double* K, int64_t ldk, int64_t n, const double* Qt, int64_t ldq, int64_t rows,
+                           double* Yt, int64_t ldy, void* workspace, int64_t ws_bytes, void* stream);
+
 /*
  * Marker effects on the standardised locus rows: B[t, j] = (Zt_j · a_t)/(q·sd_j) for kept
  * loci, 0 otherwise (B nrhs x ldb row-major), and msum[t] = Σ_j mean_j B[t, j] over this
@@ -566,6 +584,37 @@ int gbm_session_gwas(gbm_session* s, const int64_t* idx, int64_t n_train, const 
                      int64_t ldc, int64_t kc, int model, double sigma2_e, double sigma2_u, double* z_out,
                      double* b_out, double* sigma2_out, int64_t* tested_out);
 
+/* Leading eigenpairs of the relationship matrix of the rows idx[0..n_train) on the device (the population-structure
+ * covariates of a GWAS; reference gwasols' PC1, src/gwas.jl:130,234), from the cached GRM: no n² download.
+ *   kind GBM_PCS_GRM:       M = K = ZZᵀ/q, the matrix gbm_session_gwas uses;
+ *   kind GBM_PCS_REFERENCE: M = K̃HK̃ᵀ with K̃ = (K − 1mᵀ)D⁻¹ (K's columns standardised: m the column means, D the
+ *     ddof-1 column standard deviations) and H = I − 11ᵀ/n: the matrix whose first eigenvector the reference's
+ *     fit(PCA, K̃; maxoutdim = 1) returns. M is never formed: MQ = KW − 1(mᵀW), W = D⁻¹H D⁻¹(KQ − m(1ᵀQ)), two
+ *     products with K. GBM_E_DATA when a column of K has a standard deviation <= eps·(the largest).
+ * Iteration: an orthonormal block Q of 32 vectors (start: a fixed counter-hash block); Y = MQ
+ * (gbm_dev_rows_times_sym); T = QᵀY = SΘSᵀ on the host (cyclic Jacobi, gbm_debug_sym_eig); Ritz residuals
+ * r_i = ‖Y s_i − θ_i Q s_i‖₂/θ_1 for i < k on the device; stop when max_i r_i < tol or after max_iter iterations;
+ * otherwise Q = Y orthonormalised (CholQR, twice). 1 <= k <= 16, n_train >= 64.
+ * The block is always 32 wide, whatever k: GBM_E_DATA ("the block lost rank") when a Cholesky pivot of a CholQR pass
+ * falls to 1e-13 of its diagonal entry, i.e. when M has fewer than 32 eigenvalues that the block can tell from zero
+ * (fewer than about 31 polymorphic loci, since rank K <= q and rank K̃HK̃ᵀ <= q + 1; or a spectrum that decays
+ * past about 3e-7·λ₁ within the 32 leading values), also for k = 1; nothing is written to the outputs then. Also
+ * GBM_E_DATA: a NaN/Inf in the projected matrix, or no positive Ritz value. A caller with such inputs takes the
+ * eigenvectors on the host (as gbm.gwas.gwasols does).
+ * vecs_out (n_train x k column-major): v_i = Q s_i with unit 2-norm, signed so that its component of largest
+ * magnitude is positive (the lowest index wins ties); vals_out (k): θ_i, descending; trace_out (may be NULL): tr M
+ * (kind 0: Σ K_ii, so θ_i/trace is the explained share); resid_out (k, may be NULL): the r_i of the last iteration;
+ * iters_out (may be NULL): iterations run. Reaching max_iter returns GBM_OK with resid_out above tol, and
+ * gbm_last_error() then starts with "warning:" (it is "" after a converged call). Deterministic: two calls give the
+ * same bits. The training set is cached as by gbm_session_gblup_fit (a later fit or scan on the same idx is a cache
+ * hit with unchanged bits); the cached Z and GRM are not written, the symmetric K lives in the solve's scratch copy. */
+#define GBM_PCS_GRM 0
+#define GBM_PCS_REFERENCE 1
+int gbm_session_pcs(gbm_session* s, const int64_t* idx, int64_t n_train, int kind, int64_t k, double tol,
+                    int64_t max_iter, double* vecs_out /* n_train x k column-major */, double* vals_out /* k */,
+                    double* trace_out /* may be NULL */, double* resid_out /* k, may be NULL */,
+                    int64_t* iters_out /* may be NULL */);
+
 /*
  * ---- Bayesian ridge regression (BGLR model "BRR") by Gibbs sampling -------------------------
  * Replaces the Rscript/BGLR call of reference bglr()/bayesian() (src/bayes.jl:28-105,158-224)
@@ -681,6 +730,10 @@ int gbm_debug_xg_choose(double wmin, double wmax, int* slices_out, int* shift_ou
  * GBM_E_ARG unless name starts with "GBM_". */
 int gbm_debug_set(const char* name, const char* value);
 
+/* Eigen-decomposition of the symmetric m x m matrix A (1 <= m <= 64; (A + Aᵀ)/2 is used) by the cyclic Jacobi
+ * method gbm_session_pcs runs on its 32 x 32 projected matrix (host only, no device work): w (m) descending,
+ * V (m x m): V[i·m + r] = component r of the unit eigenvector of w[i]. */
+int gbm_debug_sym_eig(const double* A, int m, double* w, double* V);
 #ifdef __cplusplus
 }
 #endif
