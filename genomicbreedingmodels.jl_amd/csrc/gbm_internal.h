@@ -176,6 +176,24 @@ int launch_pcs_resid(const double* St, const double* Q, int64_t ldq, const doubl
                      double* part, hipStream_t st);
 int launch_pcs_start(double* Q, int64_t ldq, int64_t n, uint64_t seed, hipStream_t st);
 
+// Epistasis feature scan (pairscan.hip; driver: gbm_session_pair_scan). W is l x ldw locus-major with
+// ldw = pair_scan_ldw(n). launch_pair_scan: the slopes of the i-rows [i0, i0 + rows) into beta (rows x l; unary
+// operations: li = rows = 1, else li = l) and the counters cnt[0..2] (tested, degenerate, non-finite).
+// launch_pair_select: the k largest |beta| > eps of a panel's m slopes into cand_idx (base + index) / cand_beta;
+// state: pair_sel_state_bytes() (its last 16 bytes: the counts above and equal to the k-th value),
+// blk: 2·pair_sel_blocks(m) int64.
+int64_t pair_scan_ldw(int64_t n);
+int64_t pair_sel_blocks(int64_t m);
+int64_t pair_sel_state_bytes();
+int launch_pair_prep(const double* Xt, int64_t ldx, const int64_t* idx, int64_t n, const int64_t* loci, int64_t l,
+                     double eps, int use_abs, double var_threshold, const double* y, double ybar, double* W,
+                     int64_t ldw, double* var, int32_t* skip, double* yc, hipStream_t s);
+int launch_pair_scan(int op, const double* W, int64_t ldw, int64_t n, int64_t l, int64_t li, int64_t i0, int64_t rows,
+                     const double* yc, const int32_t* skip, int commutative, double* beta, unsigned long long* cnt,
+                     hipStream_t s);
+int launch_pair_select(const double* beta, int64_t m, int64_t base, double eps, int64_t k, void* state, int64_t* blk,
+                       int64_t* cand_idx, double* cand_beta, hipStream_t s);
+
 // REML choice of λ (session.cpp; reference loglikreml src/gwas.jl:450-483 with X = 1)
 struct RemlEval {
   double g, s2u, s2e;  // objective, σ²_u, σ²_e at one λ (σ²_u profiled inside the box [eps, 1]²)

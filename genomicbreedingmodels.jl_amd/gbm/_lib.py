@@ -48,12 +48,14 @@ EXPORTS = (
     "gbm_debug_chol_flow_order_check", "gbm_debug_chol_flow_order_size", "gbm_dev_grm_exact_status", "gbm_debug_set",
     "gbm_dev_whiten_rows", "gbm_session_gwas", "gbm_session_enet_path", "gbm_dev_standardize_grm_syrk",
     "gbm_dev_grm_symmetrize", "gbm_dev_rows_times_sym", "gbm_dev_rows_times_sym_workspace", "gbm_session_pcs",
-    "gbm_debug_sym_eig",
+    "gbm_debug_sym_eig", "gbm_session_pair_scan",
 )
 
 GBM_GRM_DEFAULT, GBM_GRM_FP64, GBM_GRM_EXACT, GBM_GRM_AUTO, GBM_GRM_DROPIN = -1, 0, 1, 2, 3
 GBM_PCS_GRM, GBM_PCS_REFERENCE = 0, 1
 PCS_KINDS = {"grm": GBM_PCS_GRM, "reference": GBM_PCS_REFERENCE}
+# GBM_PAIR_OP_* by the reference's function names (src/transformation.jl:9-54); the last three are unary
+PAIR_OPS = {"mult": 0, "addnorm": 1, "raise": 2, "square": 3, "invoneplus": 4, "log10epsdivlog10eps": 5}
 GRM_MODES = {None: GBM_GRM_DEFAULT, "default": GBM_GRM_DEFAULT, "fp64": GBM_GRM_FP64, "exact": GBM_GRM_EXACT,
              "auto": GBM_GRM_AUTO, "dropin": GBM_GRM_DROPIN}
 
@@ -259,6 +261,8 @@ def _declare(lib):
     lib.gbm_dev_rows_times_sym.argtypes = [P, I64, I64, P, I64, I64, P, I64, P, I64, P]
     lib.gbm_session_pcs.restype = I32
     lib.gbm_session_pcs.argtypes = [P, P, I64, I32, I64, D, I64, P, P, P, P, P]
+    lib.gbm_session_pair_scan.restype = I32
+    lib.gbm_session_pair_scan.argtypes = [P, P, I64, P, P, I64, I32, D, I32, D, I32, I64, I64, P, P, P, P, P, P]
     lib.gbm_debug_sym_eig.restype = I32
     lib.gbm_debug_sym_eig.argtypes = [P, I32, P, P]
     lib.gbm_debug_set.restype = I32

@@ -248,6 +248,64 @@ class GenotypeSession:
         return {"z": z, "b": b, "sigma2_e": None if m else float(used[0]), "sigma2_u": None if m else float(used[1]),
                 "tested": int(tested[0])}
 
+    def pair_scan(self, idx, y, op, *, loci=None, eps: float = float(np.finfo(np.float64).eps), use_abs: bool = False,
+                  var_threshold: float = 0.01, commutative: bool = False, k: int = 1000, panel_rows: int = 0,
+                  full: bool = False) -> dict:
+        """Epistasis feature scan on rows ``idx`` (gbm_session_pair_scan; reference transform1 / transform2,
+        src/transformation.jl:130-468): the slope of y ~ [1, f] for f = op(x_i, x_j) over all ordered pairs of the
+        loci ``loci`` (0-based, distinct; None: all p), or f = op(x_j) for the unary operations, with
+        x = X[idx, loci] + ``eps`` (absolute values with ``use_abs``). ``op``: one of the names "mult", "addnorm",
+        "raise", "square", "invoneplus", "log10epsdivlog10eps" or the function of that name in
+        :mod:`gbm.transformation`. Loci with variance below ``var_threshold`` are skipped (slope 0), as are, with
+        ``commutative``, the pairs j < i. Returns dict(index (the flat indices i·l + j, or j, of the at most ``k``
+        largest |slope| > eps, descending, ties to the lower index), beta (their slopes), tested, degenerate
+        (pairs whose feature is constant to rounding: slope 0, never selected) and, with ``full``, beta_full
+        ((l, l) or (l,)), which needs every slope in one panel). ``panel_rows`` (a multiple of 64; 0: by a 256 MB
+        budget) sets the i-rows per panel and does not change the result. A non-finite feature value raises
+        ArgumentError with the reference's advice (a larger eps and/or use_abs)."""
+        idx = _idx(idx)
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+        if y.shape != (idx.size,):
+            raise ArgumentError("y must have one value per training index")
+        name = op if isinstance(op, str) else getattr(op, "__name__", None)
+        if name not in _lib.PAIR_OPS:
+            raise ArgumentError(f"op must be one of {', '.join(_lib.PAIR_OPS)} (by name or as the function of "
+                                f"gbm.transformation), got {op!r}: the scan has no CPU fallback for other functions")
+        code = _lib.PAIR_OPS[name]
+        unary = code >= 3
+        if loci is None:
+            lc, l = None, self.p
+        else:
+            lc = np.ascontiguousarray(np.asarray(loci, dtype=np.int64))
+            if lc.ndim != 1 or lc.size == 0:
+                raise ArgumentError("loci must be a non-empty 1-D array")
+            l = lc.size
+        k = int(k)
+        nslopes = l if unary else l * l
+        if not 1 <= k <= 65536 or k > nslopes:
+            raise ArgumentError(f"k must be in [1, 65536] and at most the number of slopes ({nslopes}), got {k}")
+        top_i = np.zeros(k, dtype=np.int64)
+        top_b = np.zeros(k)
+        meta = np.zeros(3, dtype=np.int64)
+        mp = [ctypes.c_void_p(meta.ctypes.data + 8 * j) for j in range(3)]
+        beta = np.zeros(nslopes) if full else None
+        rc = self.lib.gbm_session_pair_scan(self._h, _lib.ptr(idx), idx.size, _lib.ptr(y), _lib.ptr(lc), l, code,
+                                            float(eps), int(bool(use_abs)), float(var_threshold),
+                                            int(bool(commutative)), int(panel_rows), k, _lib.ptr(top_i),
+                                            _lib.ptr(top_b), mp[0], _lib.ptr(beta), mp[1], mp[2])
+        if rc == _lib.GBM_E_DATA:
+            raise ArgumentError(
+                f"Cannot transform the allele frequencies using the function: `{name}`. Please consider adding a "
+                f"larger `ϵ` (currently equal to {eps}) and/or using absolute values, i.e. use `use_abs=true` "
+                f"(currently equal to {str(bool(use_abs)).lower()}). [{_lib.last_error()}]")
+        _lib.check(rc, "gbm_session_pair_scan")
+        nt = int(meta[0])
+        out = {"index": top_i[:nt].copy(), "beta": top_b[:nt].copy(), "tested": int(meta[1]),
+               "degenerate": int(meta[2])}
+        if full:
+            out["beta_full"] = beta if unary else beta.reshape(l, l)
+        return out
+
     def ridge_lambda_max(self, idx, y) -> float:
         """glmnet's first λ for alpha = 0 on rows ``idx`` (standardize = false)."""
         idx = _idx(idx)

@@ -615,6 +615,60 @@ int gbm_session_pcs(gbm_session* s, const int64_t* idx, int64_t n_train, int kin
                     double* trace_out /* may be NULL */, double* resid_out /* k, may be NULL */,
                     int64_t* iters_out /* may be NULL */);
 
+/* Epistasis feature scan on the training rows idx (0-based, strictly increasing, n_train >= 3) and the loci `loci`
+ * (0-based, in range, distinct; NULL: all p, then l = p): reference transform2 (src/transformation.jl:319-468) for
+ * the binary operations and transform1 (:130-238) for the unary ones, without their l² (l) least-squares calls.
+ * Model: with x_j = X[idx, loci[j]] + eps (|·| of that when use_abs), yc = y − ȳ and f = op(x_i, x_j) (binary) or
+ * op(x_j) (unary), the slope of [1, f] \ y is β = S_fy/S_ff, S_fy = Σ_k (f_k − f̄) yc_k, S_ff = Σ_k (f_k − f̄)².
+ * Binary: β of the l² ordered pairs, flat index i·l + j, i = j included; with `commutative` only j >= i is computed
+ * and the rest are 0 (:374-379). Unary: l slopes, flat index j; `commutative` must be 0.
+ * A locus whose ddof-1 variance of x_j is below var_threshold is skipped: every pair that holds it has β = 0
+ * (:382-387; :181-186).
+ * Accumulation: per pair Σ(f − c), Σ(f − c)² and Σ(f − c)·yc over k < n_train in the order k = 0, 1, …, with the
+ * shift c = the pair's own mean of f over its first min(n_train, 32) rows: c lies within the spread of f, so
+ * S_ff = Σ(f − c)² − (Σ(f − c))²/n does not cancel (f at k = 0 alone can be an outlier: x = 0 under
+ * log10epsdivlog10eps gives f = 0.98 among values near 0.02, which cost a factor 40 in S_ff's rounding);
+ * S_fy = Σ(f − c)·yc − (Σ(f − c)/n)·Σyc with Σyc the sum of the rounded yc in the same order, which is Σ(f − f̄)·yc:
+ * the rounding of ȳ does not enter the slope; Σf² = Σ(f − c)² + 2cΣ(f − c) + nc².
+ * Degenerate rule (a deliberate difference): the reference solves [1, f] \ y by pivoted QR (Julia's ldiv! for
+ * QRPivoted) with rcond = min(size)·eps = 2·eps; for [1, f] the squared ratio of R's diagonal is
+ * n·S_ff/max(n, Σf²)². A pair with n·S_ff <= (2·eps)²·max(n, Σf²)² is declared degenerate here: β = 0, counted in
+ * *degenerate_out, never selected. The reference returns the minimum-norm slope there (a constant feature such
+ * as addnorm(x, 1 − x) gets β ≈ 0.4·ȳ and can be selected). The rcond value and the behaviour at the boundary are
+ * unpinned against Julia (no Julia build was available to run them).
+ * Non-finite f (raise of a negative base, log10 of a negative number, 1/(1 + x) at x = −1, …): seen through the
+ * pair's sums; any tested pair with a non-finite sum or slope (an overflow of Σ(f − c)² among them) makes the call
+ * return GBM_E_DATA (reference: ArgumentError asking for a larger ϵ / use_abs, :391-405); nothing is written.
+ * Selection: the k (1 <= k <= 65 536, k <= the number of slopes) largest |β| among the slopes with |β| > eps, in
+ * descending |β|, ties to the lower flat index: the reference's stable sortperm(abs.(β), rev = true)[1:k] followed
+ * by its > ϵ filter (:420-428). top_index_out / top_beta_out (k each) receive *n_top_out <= k entries.
+ * Panels: the slopes are computed in panels of i-rows, panel_rows of them (a multiple of 64; 0: as many as keep a
+ * panel's slopes under 256 MB, at least 64); each panel yields its own k candidates on the device and the host
+ * merges the panels' candidates by the same rule, so the result does not depend on panel_rows. beta_out (l·l
+ * row-major [i·l + j], or l; may be NULL) receives every slope and is allowed only when one panel holds them all
+ * (GBM_E_ARG otherwise). tested_out / degenerate_out (may be NULL): pairs whose sums were formed (not skipped, not
+ * below the diagonal under `commutative`), and the degenerate ones among them.
+ * Determinism: one thread owns a pair and adds its terms in one fixed order that does not depend on the pair's
+ * place in the grid, so two pairs with bitwise equal columns get bitwise equal β, as do (i, j) and (j, i) under
+ * mult and addnorm, and two calls return the same bits.
+ * GBM_E_ARG: a bad op, k, idx, loci, panel_rows, n_train < 3, eps negative or not finite, NaN/Inf in y.
+ * The scan does not touch the session's training-set cache (a later fit on the same idx is a hit or a miss exactly
+ * as without the scan, with unchanged bits).
+ * Other differences from the reference: f is evaluated by the device's pow / log10 (last-ulp differences); pairs
+ * that hold a skipped locus or lie below the diagonal are evaluated and discarded, never reported. */
+#define GBM_PAIR_OP_MULT 0
+#define GBM_PAIR_OP_ADDNORM 1
+#define GBM_PAIR_OP_RAISE 2
+#define GBM_PAIR_OP_SQUARE 3
+#define GBM_PAIR_OP_INVONEPLUS 4
+#define GBM_PAIR_OP_LOG10EPS 5
+int gbm_session_pair_scan(gbm_session* s, const int64_t* idx, int64_t n_train, const double* y,
+                          const int64_t* loci /* NULL = all p */, int64_t l, int op, double eps, int use_abs,
+                          double var_threshold, int commutative, int64_t panel_rows /* 0 = by budget */,
+                          int64_t k, int64_t* top_index_out, double* top_beta_out, int64_t* n_top_out,
+                          double* beta_out /* l*l (binary) or l (unary), may be NULL */,
+                          int64_t* tested_out, int64_t* degenerate_out);
+
 /*
  * ---- Bayesian ridge regression (BGLR model "BRR") by Gibbs sampling -------------------------
  * Replaces the Rscript/BGLR call of reference bglr()/bayesian() (src/bayes.jl:28-105,158-224)
