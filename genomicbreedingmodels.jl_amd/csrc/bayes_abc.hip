@@ -1,0 +1,440 @@
+// BayesA, BayesB and BayesC by Gibbs sampling (gbm_bayes_fit, the models behind reference
+// src/linear.jl:440-626; include/gbm.h states the sampler). They reuse the per-launch skeleton of
+// BRR (brr.hip) and its setup, pooled context and graph replay (gibbs_setup.hip, gibbs_common.h),
+// but their indicator draw is not affine in x_kᵀe: a block's 64 steps run as a serial chain on the
+// block's Gram matrix (bayes_chain_kernel).
+//
+// Marker j has an effect b_j, an inclusion indicator d_j (BayesA: always 1) and (A, B) its own
+// variance varB_j. The indicator's probability is a non-linear function of x_jᵀe at the marker's
+// turn, so a block's 64 single-site steps are no triangular solve (no δ = M r̃): they run as a
+// serial chain on wave 0 of every chunk workgroup, lane k holding r_k = x_kᵀe + x2_k d_k b_k and
+// column k of the block's Gram matrix. bayes_prep_kernel forms, for every marker and in parallel,
+// everything of its step that does not depend on the chain (the normal, logit(u), 1/C, the square
+// roots), so that a chain step is FMAs, one compare, selects and one lane broadcast.
+#include "gibbs_common.h"
+
+namespace gbm {
+namespace {
+
+// the intercept step of brr_mu_kernel on the stream A = 8 it
+__global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, int64_t n,
+                                                        BayesState* __restrict__ st) {
+  __shared__ double red[16];
+  const double mu_old = st->mu;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) s += e[i] + mu_old;
+  s = brr_block_sum<1024>(s, red);
+  const double varE = st->varE;
+  const double mu = s / (double)n + sqrt(varE / (double)n) * brr_normal(st->seed, 8 * (uint64_t)st->it, 0xFFFFFFFFull);
+  for (int64_t i = threadIdx.x; i < n; i += 1024) e[i] = (e[i] + mu_old) - mu;
+  __syncthreads();
+  if (threadIdx.x == 0) st->mu = mu;
+}
+
+// Per marker j (one thread each, padded to whole blocks with zeros), the step constants pk[8 j ..]:
+//   0: x2 eff   1: eff = d b (old)   2: a = 1/(varE C)   3: c = sqrt(1/C) ξ   4: sqrt(varB) ξ
+//   5: b/(2 varE)   6: −b x2   7: log(π/(1−π)) − logit(u)
+// so that with r = x_jᵀe + x2 eff:  logOdds − logit(u) = pk5 (2 r + pk6) + pk7,  b_in = a r + c.
+// BayesA: pk5 = pk6 = 0, pk7 = 1 (always included).
+__global__ void __launch_bounds__(256) bayes_prep_kernel(int64_t p, int64_t ppad, const double* __restrict__ x2,
+                                                         const double* __restrict__ b, const double* __restrict__ d,
+                                                         const double* __restrict__ varB,
+                                                         const BayesState* __restrict__ st, double* __restrict__ pk) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= ppad) return;
+  double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (j < p) {
+    const int64_t par = st->it & 1;
+    const uint64_t A = 8 * (uint64_t)st->it;
+    const double varE = st->varE, iv = 1.0 / varE;
+    const double vb = st->model == GBM_BAYES_C ? st->varBc : varB[j];
+    const double bo = b[par * p + j], eff = d[par * p + j] * bo, xx = x2[j];
+    const double xi = brr_normal(st->seed, A, (uint64_t)j);
+    const double ic = 1.0 / (xx / varE + 1.0 / vb);
+    q[0] = xx * eff;
+    q[1] = eff;
+    q[2] = iv * ic;
+    q[3] = sqrt(ic) * xi;
+    q[4] = sqrt(vb) * xi;
+    if (st->model == GBM_BAYES_A) {
+      q[7] = 1.0;
+    } else {
+      const double u = brr_u01(st->seed, A + 3, (uint64_t)j), pi = st->pi;
+      q[5] = bo * (0.5 * iv);
+      q[6] = -bo * xx;
+      q[7] = log(pi / (1.0 - pi)) - log(u / (1.0 - u));
+    }
+  }
+  double2* out = reinterpret_cast<double2*>(pk + 8 * j);
+#pragma unroll
+  for (int u = 0; u < 4; u++) out[u] = make_double2(q[2 * u], q[2 * u + 1]);
+}
+
+// One block of 64 markers, brr_step_kernel's skeleton with the GEMV δ = M r̃ replaced by the serial
+// chain: d⁰ = Σ_c partial_in[c] (fixed order), r_k = d⁰_k + x2_k eff_k; step s broadcasts lane s's
+// δ_s = eff_s − d_new b_new and the lanes k > s do r_k += δ_s W[s][k] (lane k holds W[·][k] with
+// the entries s >= k zeroed, so a lane's r stops changing at its own step and its draw can be
+// formed again from it after the chain: same operands, same bits as the value it broadcast). Wave 0
+// of every workgroup runs the chain from identical inputs; then e += X_B δ and the next block's
+// partials as in brr_step_kernel. Workgroup 0 stores b, d and the running means of d b and d.
+template <typename T>
+__global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ Xt, int64_t ldx, int64_t n,
+                                                          int64_t p, double xs, const double* __restrict__ W,
+                                                          int64_t blk, int64_t nblk,
+                                                          const double* __restrict__ partial_in,
+                                                          double* __restrict__ partial_out,
+                                                          const double* __restrict__ pk, double* __restrict__ b,
+                                                          double* __restrict__ d, double* __restrict__ bbar,
+                                                          double* __restrict__ dbar, double* __restrict__ e,
+                                                          const BayesState* __restrict__ st) {
+  constexpr int RP = IW + 2;  // doubles (row pitch 2064 B, as brr_step_kernel)
+  __shared__ __attribute__((aligned(16))) double Xn[BB * RP];
+  __shared__ double delta[BB];
+  __shared__ double es[IW];
+  __shared__ double part4[4][BB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t j0 = blk * BB;
+  const int nb = (int)((p - j0) < BB ? (p - j0) : BB);
+  const int C = (int)gridDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * IW;
+  const int64_t i = i0 + tid;
+  const bool more = blk + 1 < nblk;
+  const int64_t j1 = j0 + BB;
+  const int nb1 = more ? (int)((p - j1) < BB ? (p - j1) : BB) : 0;
+  // (1) the next block's rows into LDS
+  uint8_t* Xb = reinterpret_cast<uint8_t*>(Xn);  // byte storage: rows of IW bytes, unpadded
+  if constexpr (sizeof(T) == 8) {
+    for (int q = wave; q < 2 * nb1; q += 4) {
+      const int k = q >> 1, h = q & 1;
+      const T* src = Xt + (j1 + k) * ldx + i0 + h * 128 + lane * 2;
+      __builtin_amdgcn_global_load_lds((const void*)src, (void*)(Xn + k * RP + h * 128), 16, 0, 0);
+    }
+  } else {
+    // 4 rows per wave instruction: lane = 16 (row within the four) + c writes LDS chunk c of its
+    // row, loaded from the row's 16-byte chunk c ^ (r & 15) (so chunk g of row r sits at position
+    // g ^ (r & 15) and the partials loop's lanes, one row each, read distinct banks). Rows past the
+    // block re-read row nb1 − 1: valid memory, never summed.
+    for (int q = wave; q < (nb1 + 3) / 4; q += 4) {
+      const int r = 4 * q + (lane >> 4), c = lane & 15;
+      const T* src = Xt + (j1 + (r < nb1 ? r : nb1 - 1)) * ldx + i0 + ((c ^ (r & 15)) * 16);
+      __builtin_amdgcn_global_load_lds((const void*)src, (void*)(Xb + q * 4 * IW), 16, 0, 0);
+    }
+  }
+  // (2) this thread's 64 genotypes of the block (rows past p clamped; their δ = 0)
+  double xv[BB];
+#pragma unroll
+  for (int s2 = 0; s2 < BB; s2++) xv[s2] = gval<T>(Xt[(j0 + (s2 < nb ? s2 : 0)) * ldx + i], xs);
+  const double e_old = e[i];
+  // (3) wave 0's operands: column `lane` of W (= its row: W is symmetric) and the step constants
+  double w[BB];
+  double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bool on = lane < nb;
+  const int64_t j = j0 + lane;
+  if (tid < 64) {
+    const double* wr = W + (blk * BB + lane) * BB;
+#pragma unroll
+    for (int s = 0; s < BB; s += 2) {
+      const double2 v = *reinterpret_cast<const double2*>(wr + s);
+      w[s] = v.x;
+      w[s + 1] = v.y;
+    }
+    const double2* pq = reinterpret_cast<const double2*>(pk + 8 * j);  // padded to whole blocks
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const double2 v = pq[u];
+      q[2 * u] = v.x;
+      q[2 * u + 1] = v.y;
+    }
+  }
+  const bool keeper = blockIdx.x == 0 && tid < 64 && on;
+  const double bb_old = keeper ? bbar[j] : 0.0, db_old = keeper ? dbar[j] : 0.0;
+  {
+    double a = 0.0;
+    for (int c0 = wave; c0 < C; c0 += 64) {
+      double v[16];
+#pragma unroll
+      for (int m = 0; m < 16; m++) v[m] = partial_in[min(c0 + 4 * m, C - 1) * BB + lane];  // unconditional loads
+#pragma unroll
+      for (int m = 0; m < 16; m++) a += c0 + 4 * m < C ? v[m] : 0.0;
+    }
+    part4[wave][lane] = a;
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const double d0 = ((part4[0][lane] + part4[1][lane]) + part4[2][lane]) + part4[3][lane];
+#pragma unroll
+    for (int s = 0; s < BB; s++) w[s] = lane > s ? w[s] : 0.0;
+    const double eff = q[1], qa = q[2], qc = q[3], bout = q[4], qbh = q[5], qm = q[6], qthr = q[7];
+    double r = d0 + q[0];
+#pragma unroll
+    for (int s = 0; s < BB; s++) {
+      const double lo = fma(qbh, fma(2.0, r, qm), qthr);
+      const double bin = fma(r, qa, qc);
+      const double cand = lo > 0.0 ? eff - bin : eff;
+      r = fma(readlane_f64(cand, s), w[s], r);
+    }
+    const double lo = fma(qbh, fma(2.0, r, qm), qthr);
+    const double bin = fma(r, qa, qc);
+    const bool inc = lo > 0.0;
+    delta[lane] = inc ? eff - bin : eff;
+    if (keeper) {
+      const double bfin = inc ? bin : bout, dfin = inc ? 1.0 : 0.0;
+      const int64_t o = ((st->it & 1) ^ 1) * p + j;
+      b[o] = bfin;
+      d[o] = dfin;
+      if (brr_accumulate(st)) {
+        const double k = (double)(st->nsum + 1);
+        bbar[j] = bb_old * ((k - 1.0) / k) + (inc ? bfin : 0.0) / k;
+        dbar[j] = db_old * ((k - 1.0) / k) + dfin / k;
+      }
+    }
+  }
+  __syncthreads();
+  double ei = 0.0;
+  if (i < n) {
+    double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+    for (int s2 = 0; s2 < BB; s2 += 2) {
+      acc0 = fma(delta[s2], xv[s2], acc0);
+      acc1 = fma(delta[s2 + 1], xv[s2 + 1], acc1);
+    }
+    ei = e_old + (acc0 + acc1);
+    e[i] = ei;
+  }
+  if (more) {
+    es[tid] = ei;
+    __syncthreads();  // also completes the global_load_lds of Xn
+    double s0 = 0.0, s1 = 0.0;
+    if (lane < nb1) {
+      const double* er = es + wave * 64;
+      if constexpr (sizeof(T) == 8) {
+        const double* xr = Xn + lane * RP + wave * 64;
+#pragma unroll
+        for (int u = 0; u < 64; u += 2) {
+          const double2 xv2 = *reinterpret_cast<const double2*>(xr + u);
+          s0 = fma(xv2.x, er[u], s0);
+          s1 = fma(xv2.y, er[u + 1], s1);
+        }
+      } else {
+        const uint8_t* xr = Xb + lane * IW;
+        uint4 v[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) v[t] = *reinterpret_cast<const uint4*>(xr + (((4 * wave + t) ^ (lane & 15)) * 16));
+        brr_dot64_u8(v, er, s0, s1);
+        s0 *= xs;
+        s1 *= xs;
+      }
+    }
+    part4[wave][lane] = s0 + s1;
+    __syncthreads();
+    if (tid < 64)
+      partial_out[blockIdx.x * BB + lane] = ((part4[0][lane] + part4[1][lane]) + part4[2][lane]) + part4[3][lane];
+  }
+}
+
+// Per-marker variances (BayesA, BayesB: varB_j = (S + b_j²)/χ²(df0 + 1) on the stream PM(it, j))
+// and, per workgroup, the partial sums vpart[5 blk ..] = Σ 1/varB_j, Σ d_j, Σ b_j², Σ varB_j over
+// its 256 markers and Σ e_i² over its 256 individuals (no atomics: bayes_final_kernel adds the
+// workgroups' partials in index order).
+__global__ void __launch_bounds__(256) bayes_var_kernel(const double* __restrict__ b, const double* __restrict__ d,
+                                                        double* __restrict__ varB, int64_t p,
+                                                        const double* __restrict__ e, int64_t n,
+                                                        const BayesState* __restrict__ st,
+                                                        double* __restrict__ vpart) {
+  __shared__ double red[4];
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t par = (st->it & 1) ^ 1;  // this iteration's samples
+  double v[5] = {0, 0, 0, 0, 0};
+  if (j < p) {
+    const double bj = b[par * p + j];
+    v[1] = d[par * p + j];
+    v[2] = bj * bj;
+    if (st->model != GBM_BAYES_C) {
+      const uint64_t pm = (1ull << 63) | ((uint64_t)st->it << 40) | (uint64_t)j;
+      const double vb = (st->S + v[2]) / brr_chisq(st->seed, pm, st->df0 + 1.0);
+      varB[j] = vb;
+      v[0] = 1.0 / vb;
+      v[3] = vb;
+    }
+  }
+  if (j < n) v[4] = e[j] * e[j];
+#pragma unroll
+  for (int u = 0; u < 5; u++) {
+    const double s = brr_block_sum<256>(v[u], red);
+    if (threadIdx.x == 0) vpart[5 * (int64_t)blockIdx.x + u] = s;
+  }
+}
+
+// The scalar draws of an iteration (one workgroup): S, BayesC's common varB, π, varE; the running
+// means of μ, varE, mean_j varB_j and π; next iteration.
+__global__ void __launch_bounds__(256) bayes_final_kernel(const double* __restrict__ vpart, int64_t nvb, int64_t p,
+                                                          int64_t n, BayesState* __restrict__ st) {
+  __shared__ double red[4];
+  double sum[5];
+#pragma unroll
+  for (int u = 0; u < 5; u++) {
+    double a = 0.0;
+    for (int64_t k = threadIdx.x; k < nvb; k += 256) a += vpart[5 * k + u];
+    sum[u] = brr_block_sum<256>(a, red);
+  }
+  if (threadIdx.x != 0) return;
+  const uint64_t A = 8 * (uint64_t)st->it, seed = st->seed;
+  const double df0 = st->df0, shape0 = st->shape0, rate0 = st->rate0;
+  double vbmean;
+  if (st->model == GBM_BAYES_C) {
+    const double vb = (sum[2] + st->S) / brr_chisq(seed, A + 1, df0 + (double)p);
+    st->varBc = vb;
+    st->S = brr_chisq(seed, A + 4, 2.0 * (0.5 * df0 + shape0)) / (2.0 * (1.0 / (2.0 * vb) + rate0));
+    vbmean = vb;
+  } else {
+    st->S = brr_chisq(seed, A + 4, 2.0 * (0.5 * (double)p * df0 + shape0)) / (2.0 * (0.5 * sum[0] + rate0));
+    vbmean = sum[3] / (double)p;
+  }
+  if (st->model != GBM_BAYES_A) {
+    const double m = sum[1];
+    const double g1 = 0.5 * brr_chisq(seed, A + 5, 2.0 * (m + st->cIn));
+    const double g2 = 0.5 * brr_chisq(seed, A + 6, 2.0 * (((double)p - m) + st->cOut));
+    st->pi = g1 / (g1 + g2);
+  }
+  st->varE = (sum[4] + st->S0e) / brr_chisq(seed, A + 2, df0 + (double)n);
+  if (brr_accumulate(st)) {
+    const double k = (double)(st->nsum + 1);
+    st->mubar = st->mubar * ((k - 1.0) / k) + st->mu / k;
+    st->varEbar = st->varEbar * ((k - 1.0) / k) + st->varE / k;
+    st->varBbar = st->varBbar * ((k - 1.0) / k) + vbmean / k;
+    st->pibar = st->pibar * ((k - 1.0) / k) + st->pi / k;
+    st->nsum += 1;
+  }
+  st->it += 1;
+}
+
+}  // namespace
+}  // namespace gbm
+
+using namespace gbm;
+
+// One BayesA / BayesB / BayesC fit on a leased context (include/gbm.h gbm_bayes_fit): the shared
+// setup (genotypes, column statistics, byte quantisation, Gram blocks), then per iteration the
+// linear chain prep, μ, block 0's partial dots, one chain launch per 64-marker block, the
+// variances — captured once as a graph and replayed. Never the super-block sweep or its lock; the
+// BRR path statistics are not written.
+static int bayes_fit_impl(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                          int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                          double counts, uint64_t seed, int dev, double* b_hat_out, double* y_pred_out,
+                          double* var_out, double* pip_out) {
+  BrrLease lease;
+  GBM_TRY(CtxPool<BrrCtx>::instance().acquire(dev, lease.c));
+  BrrCtx& cx = *lease.c;
+  GBM_HIP_TRY(hipSetDevice(dev));
+  hipStream_t s = cx.stream.s;
+  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB;
+  const int64_t nvb = (std::max(n, p) + 255) / 256;
+  GBM_TRY(ensure(cx.dind, dev, 2 * p * 8));  // two copies (iteration parity), as b
+  GBM_TRY(ensure(cx.dbar, dev, p * 8));
+  GBM_TRY(ensure(cx.varBj, dev, p * 8));
+  GBM_TRY(ensure(cx.pk, dev, ppad * 8 * 8));
+  GBM_TRY(ensure(cx.vpart, dev, nvb * 5 * 8));
+  GBM_TRY(ensure(cx.bst, dev, sizeof(BayesState)));
+  GibbsData g;
+  GBM_TRY(gibbs_upload(cx, X, n, p, ldx, g));
+  const int64_t npad = g.npad;
+  const double xs = g.xs;
+  GBM_TRY(gibbs_gram(cx, n, p, npad, nblk, 1));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  GibbsPrior pr;
+  GBM_TRY(gibbs_prior("gbm_bayes_fit", y, n, p, g, pr));
+  const double shape0 = 1.1;
+  double S0 = pr.vy * r2 / pr.msx * (df0 + 2.0);
+  if (model != GBM_BAYES_A) S0 /= prob_in;
+  BayesState st0{};
+  st0.mu = pr.ym;
+  st0.S0e = pr.vy * (1.0 - r2) * (df0 + 2.0);
+  st0.varE = st0.S0e / (df0 + 2.0);
+  st0.S = S0;
+  st0.varBc = S0 / (df0 + 2.0);
+  st0.rate0 = (shape0 - 1.0) / S0;
+  st0.shape0 = shape0;
+  st0.df0 = df0;
+  st0.pi = prob_in;
+  st0.cIn = counts * prob_in;
+  st0.cOut = counts * (1.0 - prob_in);
+  st0.burnin = n_burnin;
+  st0.thin = thin;
+  st0.seed = seed;
+  st0.model = model;
+  std::vector<double> init(2 * p, 1.0);  // d = 1; then varB_j = S0/(df0 + 2)
+  GBM_HIP_TRY(hipMemcpyAsync(cx.e.p, pr.e0.data(), npad * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.dind.p, init.data(), 2 * p * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  std::fill(init.begin(), init.begin() + p, st0.varBc);
+  GBM_HIP_TRY(hipMemcpyAsync(cx.varBj.p, init.data(), p * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemsetAsync(cx.b.p, 0, 2 * p * 8, s));
+  GBM_HIP_TRY(hipMemsetAsync(cx.bbar.p, 0, p * 8, s));
+  GBM_HIP_TRY(hipMemsetAsync(cx.dbar.p, 0, p * 8, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.bst.p, &st0, sizeof(BayesState), hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  auto* stp = (BayesState*)cx.bst.p;
+  const unsigned C = (unsigned)g.C64;
+  auto enqueue_iteration = [&]() -> int {
+    bayes_prep_kernel<<<(unsigned)(ppad / 256 + 1), 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
+                                                                 (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
+                                                                 (double*)cx.pk.p);
+    bayes_mu_kernel<<<1, 1024, 0, s>>>((double*)cx.e.p, n, stp);
+    gibbs_dots0(cx, n, p, g, xs > 0.0);
+    for (int64_t k = 0; k < nblk; k++) {
+      double* pin = (double*)cx.r.p + (k & 1) * (int64_t)C * BB;
+      double* pout = (double*)cx.r.p + ((k + 1) & 1) * (int64_t)C * BB;
+      if (xs > 0.0)
+        bayes_chain_kernel<uint8_t><<<C, 256, 0, s>>>((const uint8_t*)cx.D.p, npad, n, p, xs, (const double*)cx.W.p, k,
+                                                      nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
+                                                      (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+                                                      (double*)cx.e.p, stp);
+      else
+        bayes_chain_kernel<double><<<C, 256, 0, s>>>((const double*)cx.Xt.p, npad, n, p, 1.0, (const double*)cx.W.p, k,
+                                                     nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
+                                                     (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+                                                     (double*)cx.e.p, stp);
+    }
+    bayes_var_kernel<<<(unsigned)nvb, 256, 0, s>>>((const double*)cx.b.p, (const double*)cx.dind.p, (double*)cx.varBj.p, p,
+                                                   (const double*)cx.e.p, n, stp, (double*)cx.vpart.p);
+    bayes_final_kernel<<<1, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp);
+    return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, "gbm_bayes_fit: launch failed");
+  };
+  cx.bayes_graph.ensure({model, n, p, npad, (int64_t)(xs * 64.0), key_of(cx.Xt), key_of(cx.D), key_of(cx.W),
+                         key_of(cx.r), key_of(cx.e), key_of(cx.b), key_of(cx.dind), key_of(cx.bbar), key_of(cx.dbar),
+                         key_of(cx.varBj), key_of(cx.pk), key_of(cx.vpart), key_of(cx.x2), key_of(cx.bst)},
+                        s, enqueue_iteration);
+  GBM_TRY(cx.bayes_graph.run(n_iter, s, "gbm_bayes_fit", enqueue_iteration));
+  BayesState fin{};
+  GBM_TRY(gibbs_outputs(cx, n, p, npad, cx.bst, &fin, sizeof(fin), &fin.mubar, b_hat_out, pip_out, y_pred_out));
+  if (var_out) {
+    var_out[0] = fin.varEbar;
+    var_out[1] = fin.varBbar;
+    var_out[2] = fin.pibar;
+  }
+  return GBM_OK;
+}
+
+extern "C" int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                             int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                             double counts, uint64_t seed, int device, double* b_hat_out, double* y_pred_out,
+                             double* var_out, double* pip_out) {
+  RoctxRange r_("gbm_bayes_fit");
+  set_error("");
+  if (model != GBM_BAYES_A && model != GBM_BAYES_B && model != GBM_BAYES_C)
+    return fail(GBM_E_ARG, "gbm_bayes_fit: model must be GBM_BAYES_A, GBM_BAYES_B or GBM_BAYES_C");
+  GBM_TRY(gibbs_check_args("gbm_bayes_fit", X, y, b_hat_out, n, p, ldx, n_iter, n_burnin, thin, r2, df0));
+  // the gamma sampler (Marsaglia-Tsang) needs shapes >= 1: (df0 + 1)/2 of the per-marker variances
+  // and counts·prob_in, counts·(1 − prob_in) of π's Beta draw
+  if (!(df0 >= 1.0) || !(prob_in > 0.0 && prob_in < 1.0) || !(counts * prob_in >= 1.0) ||
+      !(counts * (1.0 - prob_in) >= 1.0))
+    return fail(GBM_E_ARG, "gbm_bayes_fit: bad prior (df0 >= 1, 0 < prob_in < 1, counts*prob_in >= 1, "
+                           "counts*(1 - prob_in) >= 1)");
+  // the per-marker random streams are (iteration, marker) packed into 23 + 40 bits
+  if (n_iter > ((int64_t)1 << 23) || p >= ((int64_t)1 << 40))
+    return fail(GBM_E_ARG, "gbm_bayes_fit: n_iter <= 2^23 and p < 2^40");
+  int dev = 0;
+  GBM_TRY(gibbs_check_run("gbm_bayes_fit", y, n, n_iter, n_burnin, thin, device, dev));
+  return bayes_fit_impl(model, X, n, p, ldx, y, n_iter, n_burnin, thin, r2, df0, prob_in, counts, seed, dev, b_hat_out,
+                        y_pred_out, var_out, pip_out);
+}

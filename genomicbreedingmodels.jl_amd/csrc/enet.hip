@@ -4,7 +4,7 @@
 //
 // The active markers' centred rows are packed in admission order into Za (A x lda fp64 locus rows,
 // lda a multiple of 256, zero past n). One coordinate-descent pass over them is one launch per
-// 64-marker block (enet_chain_kernel): bayes_chain_kernel<double>'s skeleton (gibbs.hip, DESIGN.md
+// 64-marker block (enet_chain_kernel): bayes_chain_kernel<double>'s skeleton (bayes_abc.hip, DESIGN.md
 // §4.6.1) with the soft threshold as the step. A soft threshold is piecewise affine in r, not affine,
 // so as there the block's 64 steps are no triangular solve: they run as a serial chain on wave 0 of
 // every chunk workgroup, lane k holding r_k = x_kᵀe + x2_k b_k and column k of the block's Gram

@@ -41,70 +41,7 @@ struct FitCtx {
   }
 };
 
-class CtxPool {
- public:
-  int acquire(int dev, std::unique_ptr<FitCtx>& out) {
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      auto& v = idle_[dev];
-      if (!v.empty()) {
-        out = std::move(v.back());
-        v.pop_back();
-        return GBM_OK;
-      }
-    }
-    auto c = std::make_unique<FitCtx>();
-    c->dev = dev;
-    c->stream.dev = dev;
-    GBM_HIP_TRY(hipSetDevice(dev));
-    GBM_HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
-    out = std::move(c);
-    return GBM_OK;
-  }
-  void release(std::unique_ptr<FitCtx> c) {
-    // nothing of this call may still run on the context's stream when another call takes it
-    (void)hipSetDevice(c->dev);
-    if (hipStreamSynchronize(c->stream.s) != hipSuccess) {
-      (void)hipGetLastError();
-      return;  // a broken context is dropped (its destructor frees what it can)
-    }
-    std::lock_guard<std::mutex> lock(mu_);
-    idle_[c->dev].push_back(std::move(c));
-  }
-  void clear() {
-    std::map<int, std::vector<std::unique_ptr<FitCtx>>> drop;
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      drop.swap(idle_);
-    }
-  }
-  // drops the idle contexts of one device (their buffers are freed outside the lock); returns how many
-  int64_t trim(int dev) {
-    std::vector<std::unique_ptr<FitCtx>> drop;
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      auto it = idle_.find(dev);
-      if (it != idle_.end()) drop.swap(it->second);
-    }
-    return (int64_t)drop.size();
-  }
-
- private:
-  std::mutex mu_;
-  std::map<int, std::vector<std::unique_ptr<FitCtx>>> idle_;
-};
-
-// never destroyed: pooled device memory must not be freed after the HIP runtime tears down
-inline CtxPool& pool() {
-  static CtxPool* p = [] {
-    auto* cp = new CtxPool;
-    // an allocation that runs out of device memory first frees the idle contexts of its device
-    // (they only grow and would otherwise hold e.g. ~50 GB each at C3's shape), then retries once
-    register_trim_hook([](int dev) { return pool().trim(dev); });
-    return cp;
-  }();
-  return *p;
-}
+inline CtxPool<FitCtx>& pool() { return CtxPool<FitCtx>::instance(); }
 
 // One SNP-column shard [j0, j0 + p) on a leased context.
 struct Shard {

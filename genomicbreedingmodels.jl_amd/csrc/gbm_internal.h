@@ -205,7 +205,7 @@ double reml_objective(int64_t n, double logdet, double c11, double Q, double s2u
 RemlEval reml_profile(int64_t n, double lambda, const double t[4]);
 int reml_search(const std::function<int(double, RemlEval&)>& eval, RemlResult& out);
 std::vector<double> standardise_y(const double* y, int64_t n);
-// frees the idle pooled BRR contexts (gibbs.hip; part of gbm_release_device_cache)
+// frees the idle pooled BRR contexts (gibbs_setup.hip; part of gbm_release_device_cache)
 void brr_release_cache();
 
 }  // namespace gbm

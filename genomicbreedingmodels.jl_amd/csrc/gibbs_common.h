@@ -1,0 +1,281 @@
+// What the pieces of the Gibbs samplers share (not part of the ABI; include from .hip files only):
+//   gibbs_setup.hip  the kernels, pooled context and host steps both samplers use;
+//   brr.hip          Bayesian ridge regression: the per-launch kernels, gbm_brr_fit, the debug exports;
+//   brr_sweep.hip    its persistent super-block sweep, behind brr_sweep_plan / _setup / _enqueue;
+//   bayes_abc.hip    BayesA, BayesB, BayesC: gbm_bayes_fit.
+//
+// Random numbers: a counter-based hash of (seed, stream, counter) (no sampler state), Box-Muller
+// normals and Marsaglia-Tsang gammas, restated bit-for-bit in oracle/oracle.py (brr_*), so the
+// device chains and the oracle's un-blocked BGLR loops follow the same sample path.
+#pragma once
+#include <functional>
+#include <mutex>
+#include <vector>
+
+#include "counter_hash.h"
+#include "gbm_internal.h"
+#include "host_util.h"
+
+namespace gbm {
+
+constexpr int BB = 64;  // markers per block (one wave)
+constexpr int IW = 256;  // individuals per workgroup in the block kernels
+constexpr int BK2 = 2 * BB;  // markers per launch of the byte per-launch path
+constexpr int SBK = 512;  // markers per super-block (brr_sweep.hip)
+constexpr int SBN = SBK / (2 * BB);  // 128-marker sub-blocks per super-block
+
+__device__ __forceinline__ double brr_u01(uint64_t seed, uint64_t a, uint64_t b) {
+  const uint64_t h = mix64(mix64(seed ^ (a * 0xD1B54A32D192ED03ull)) ^ (b * 0x8CB92BA72F3D8DD7ull));
+  return ((double)(h >> 11) + 0.5) * 0x1.0p-53;
+}
+__device__ __forceinline__ double brr_normal(uint64_t seed, uint64_t a, uint64_t b) {
+  const double u1 = brr_u01(seed, a, 2 * b), u2 = brr_u01(seed, a, 2 * b + 1);
+  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+// χ²(df) = 2 Gamma(df/2) by Marsaglia-Tsang (df/2 >= 1); attempt t uses normal (a, 2t) and
+// uniform (a, 4t + 2)
+__device__ inline double brr_chisq(uint64_t seed, uint64_t a, double df) {
+  const double d = 0.5 * df - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+  for (uint64_t t = 0; t < 1000; t++) {
+    const double x = brr_normal(seed, a, 2 * t);
+    double v = 1.0 + c * x;
+    if (v <= 0.0) continue;
+    v = v * v * v;
+    const double u = brr_u01(seed, a, 4 * t + 2);
+    if (log(u) < 0.5 * x * x + d - d * v + d * log(v)) return 2.0 * d * v;
+  }
+  return df;  // unreachable in practice (acceptance ≈ 0.98 per attempt)
+}
+
+struct BrrState {
+  double mu, varE, varB, S0e, S0b, df0e, df0b;
+  double mubar, varEbar, varBbar;
+  int64_t it, burnin, thin, nsum;
+  uint64_t seed;
+  uint64_t epoch;  // distinct per fit: part of the super-block sweep's hand-off tags (pooled buffers)
+};
+struct BayesState {
+  double mu, varE, varBc, S, pi;  // varBc: BayesC's common σ²_b
+  double S0e, df0, rate0, shape0, cIn, cOut;
+  double mubar, varEbar, varBbar, pibar;
+  int64_t it, burnin, thin, nsum;
+  uint64_t seed;
+  int model;  // GBM_BAYES_A, _B or _C
+};
+// the sample gate: does this iteration enter the running posterior means?
+template <typename State>
+__device__ __forceinline__ bool brr_accumulate(const State* st) {
+  const int64_t i = st->it + 1;  // BGLR's 1-based iteration
+  return (i % st->thin == 0) && (i > st->burnin);
+}
+
+template <int BS>
+__device__ __forceinline__ double brr_block_sum(double v, double* red) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int k = 0; k < BS / 64; k++) s += red[k];
+  return s;
+}
+// Workgroup barrier that waits for this wave's LDS operations only (__syncthreads also waits for
+// every outstanding global load, e.g. the next block's rows that are needed much later).
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+  __builtin_amdgcn_s_barrier();
+}
+__device__ __forceinline__ double readlane_f64(double x, int l) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, x);
+  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)u, l);
+  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
+  return __builtin_bit_cast(double, (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32));
+}
+
+// Genotype storage of the block kernels: fp64 (any allele frequencies), or bytes d with
+// x = d·xs when every x/xs is an integer in [0, 255] (xs = 1/2 for diploid dosages: exact, so
+// both storages run the identical chain with 8× fewer bytes per block for the bytes).
+// 64 byte-genotypes (4 × 16 B) times 64 values of es, accumulated in the fp64 path's order:
+// even individuals into s, odd ones into s1. The bytes are summed unscaled and the caller scales
+// both sums by xs: xs is a power of two, so (Σ d e)·xs has the bits of Σ (d·xs) e.
+__device__ __forceinline__ void brr_dot64_u8(const uint4 (&v)[4], const double* es, double& s, double& s1) {
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const uint32_t wd[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+    for (int w = 0; w < 4; w++)
+#pragma unroll
+      for (int b = 0; b < 4; b += 2) {
+        const int idx = 16 * u + 4 * w + b;
+        s = fma((double)((wd[w] >> (8 * b)) & 0xFFu), es[idx], s);
+        s1 = fma((double)((wd[w] >> (8 * b + 8)) & 0xFFu), es[idx + 1], s1);
+      }
+  }
+}
+template <typename T>
+__device__ __forceinline__ double gval(T v, double xs) {
+  if constexpr (sizeof(T) == 8) return (double)v;
+  else return (double)v * xs;
+}
+
+// partial[c][k] = Σ_{i in chunk c} x_{j0+k, i} e_i over this workgroup's IW individuals, from es
+// (the chunk of e in LDS): thread (k = tid/4, quarter) sums 64 contiguous individuals
+template <typename T>
+__device__ __forceinline__ void brr_partials(const T* __restrict__ Xt, int64_t ldx, int64_t n, int64_t i0,
+                                             int64_t j0, int nb, double xs, const double* es,
+                                             double* __restrict__ out) {
+  const int tid = threadIdx.x, k = tid >> 2, qt = tid & 3;
+  double s = 0.0;
+  if (k < nb) {
+    // 64 contiguous individuals per thread, all loads in flight (rows are zero-padded to ldx, a
+    // multiple of IW, and es is 0 past n)
+    const T* row = Xt + (j0 + k) * ldx + i0 + qt * 64;
+    double s1 = 0.0;
+    if constexpr (sizeof(T) == 8) {
+      double2 v[32];
+#pragma unroll
+      for (int u = 0; u < 32; u++) v[u] = *reinterpret_cast<const double2*>(row + 2 * u);
+#pragma unroll
+      for (int u = 0; u < 32; u++) {
+        s = fma(v[u].x, es[qt * 64 + 2 * u], s);
+        s1 = fma(v[u].y, es[qt * 64 + 2 * u + 1], s1);
+      }
+    } else {
+      uint4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) v[u] = *reinterpret_cast<const uint4*>(row + 16 * u);
+      brr_dot64_u8(v, es + qt * 64, s, s1);
+      s *= xs;
+      s1 *= xs;
+    }
+    s += s1;
+  }
+  s += __shfl_xor(s, 1);
+  s += __shfl_xor(s, 2);
+  if (qt == 0) out[blockIdx.x * BB + k] = s;  // k >= nb writes 0
+}
+
+// One 64x64 tile X_RᵀX_C of a Gram matrix for the marker rows R = [r0, r0 + 64), C = [c0, c0 + 64) of
+// Xt (rows past p are zero), by one 256-thread workgroup: individuals in chunks of 64 staged through
+// LDS, thread (a, b0) sums out[a][b0 .. b0 + 15]. out: the tile's first element, row pitch ldo.
+__device__ __forceinline__ void brr_gram_tile(const double* __restrict__ Xt, int64_t ldx, int64_t p, int64_t n,
+                                              int64_t r0, int64_t c0, double* __restrict__ out, int64_t ldo) {
+  __shared__ double TR[BB][BB + 1];
+  __shared__ double TC[BB][BB + 1];
+  const int tid = threadIdx.x, a = tid >> 2, b0 = (tid & 3) * 16;
+  double acc[16];
+#pragma unroll
+  for (int u = 0; u < 16; u++) acc[u] = 0.0;
+  for (int64_t k0 = 0; k0 < n; k0 += BB) {
+    for (int e = tid; e < BB * BB; e += 256) {
+      const int r = e / BB, c = e % BB;
+      TR[r][c] = (r0 + r < p && k0 + c < n) ? Xt[(r0 + r) * ldx + k0 + c] : 0.0;
+      TC[r][c] = (c0 + r < p && k0 + c < n) ? Xt[(c0 + r) * ldx + k0 + c] : 0.0;
+    }
+    __syncthreads();
+    for (int k = 0; k < BB; k++) {
+      const double xa = TR[a][k];
+#pragma unroll
+      for (int u = 0; u < 16; u++) acc[u] += xa * TC[b0 + u][k];
+    }
+    __syncthreads();
+  }
+  out += a * ldo + b0;
+#pragma unroll
+  for (int u = 0; u < 16; u++) out[u] = acc[u];
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+
+// One Gibbs iteration captured as a hipGraph and replayed, kept while `key` (the call's shape and
+// buffers) is unchanged; without a graph (capture or instantiation failed) run() launches directly.
+struct IterGraph {
+  hipGraphExec_t exec = nullptr;
+  hipGraph_t graph = nullptr;
+  std::vector<int64_t> key;  // what the captured graph was built for
+  void drop();
+  void ensure(const std::vector<int64_t>& k, hipStream_t s, const std::function<int()>& enqueue);
+  // n_iter iterations, then the stream synchronised; `entry` names the caller in the error text
+  int run(int64_t n_iter, hipStream_t s, const char* entry, const std::function<int()>& enqueue);
+};
+inline int64_t key_of(const DevBuf& b) { return (int64_t)(uintptr_t)b.p; }  // a buffer's entry in a graph key
+
+// Pooled per-device sampler contexts (as fit_ctx.h pools the GBLUP fit contexts): a fit leases one,
+// its buffers only grow, so repeated fits of one shape allocate no device memory after the first
+// (cvmultithread! runs bayesian("BRR") once per fold). BRR and BayesA/B/C fits that alternate on
+// one context keep both captured graphs.
+struct BrrCtx {
+  int dev = 0;
+  Stream stream;
+  DevBuf Xt, colmean, x2, e, b, bbar, r, stm, D, badm, W, Mb, alph, gamm, Dt, pb, part, pout;
+  DevBuf Wsb, MS, Ssc, Pb, Rt, Dl, sbcnt;  // the super-block sweep
+  DevBuf CS, CS2;                          // its cross-Grams C_s = X_sᵀ X_{s−1}, C2_s = X_sᵀ X_{s−2}
+  DevBuf trace;                            // GBM_BRR_TRACE timestamps of this context's last sweep
+  DevBuf dind, dbar, varBj, pk, vpart, bst;  // gbm_bayes_fit: indicators, PIP, varB_j, step constants, partial sums, state
+  IterGraph brr_graph, bayes_graph;
+  ~BrrCtx() {
+    (void)hipSetDevice(dev);
+    brr_graph.drop();
+    bayes_graph.drop();
+  }
+};
+struct BrrLease {
+  std::unique_ptr<BrrCtx> c;
+  ~BrrLease() {
+    if (c) CtxPool<BrrCtx>::instance().release(std::move(c));
+  }
+};
+
+// The checks gbm_brr_fit and gbm_bayes_fit share (`entry` opens the error text): the arguments, then
+// (after a caller's own checks) the sampling schedule, the phenotypes and the device.
+int gibbs_check_args(const char* entry, const double* X, const double* y, const double* b_hat_out, int64_t n, int64_t p,
+                     int64_t ldx, int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0);
+int gibbs_check_run(const char* entry, const double* y, int64_t n, int64_t n_iter, int64_t n_burnin, int64_t thin,
+                    int device, int& dev_out);
+
+// The genotypes of a fit on its context: X into Xt (rows padded with zeros to npad individuals),
+// column means and Σx² (cm, xx: filled once the stream has been synchronised), and byte storage D
+// where X = D·xs exactly (xs = 0: fp64 storage). Also sizes e, b, bbar and the partial dots r.
+struct GibbsData {
+  int64_t npad = 0, C64 = 0;  // individuals padded to whole IW chunks; the chunks
+  double xs = 0.0;
+  std::vector<double> cm, xx;
+};
+int gibbs_upload(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, GibbsData& g);
+// W = the Gram blocks of brr_gram_kernel (nw = 1 or 3) for nblk launches; sizes W
+int gibbs_gram(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, int64_t nblk, int nw);
+// block 0's partial dots into r, from the fp64 rows or (bytes) from D as 64-marker blocks
+void gibbs_dots0(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, bool bytes);
+// BGLR's prior moments: ȳ, var(y) with ddof 1, MSx = Σ_j var(x_j), and the start residual y − ȳ
+struct GibbsPrior {
+  double ym = 0.0, vy = 0.0, msx = 0.0;
+  std::vector<double> e0;  // npad values
+};
+int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const GibbsData& g, GibbsPrior& pr);
+// The tail of a fit: the final state (fin_bytes from `state` into fin) and the posterior means to
+// the host, b_hat_out[0] = *mubar (a field of fin), then the optional y_pred = μ̄ + X b̄.
+int gibbs_outputs(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, const DevBuf& state, void* fin, size_t fin_bytes,
+                  const double* mubar, double* b_hat_out, double* pip_out, double* y_pred_out);
+
+// ---- the super-block sweep's host interface (brr_sweep.hip) -----------------------------------------
+// The chunk shape of a sweep over n individuals on a device of `cus` CUs, per the knobs
+// GBM_BRR_SWEEP, GBM_BRR_SB_K and GBM_BRR_OWN_R (read per call): uniform chunks of K individuals on C
+// workgroups owning R rows of a super-block each, or (GBM_BRR_OWN_R) O owners of Ko and the rest Kn.
+struct SweepPlan {
+  bool on = false;  // the sweep can run: all its workgroups resident, one per CU
+  int K = 0, Cu = 0, Ru = 0;  // the uniform split
+  int Ko = 0, Kn = 0, R = 0, O = 0, C = 0;
+};
+int brr_sweep_plan(int64_t n, int cus, SweepPlan& pl);
+// one-time setup after W, Mb, α, γ are sized: the sweep's buffers, cross-Grams and super-block Gram
+// blocks (trace_n > 0: the trace buffer of a traced fit)
+int brr_sweep_setup(BrrCtx& cx, const SweepPlan& pl, int64_t n, int64_t p, int64_t npad, int64_t nsb, int64_t trace_n);
+// the sweep's share of an iteration: M_S of every super-block (three levels), then the sweep
+void brr_sweep_enqueue(BrrCtx& cx, const SweepPlan& pl, int64_t n, int64_t p, int64_t npad, int64_t nsb, double xs,
+                       int64_t* trace_dev);
+inline int32_t* brr_sweep_error_cell(BrrCtx& cx) { return (int32_t*)cx.sbcnt.p + 24; }  // zeroed at setup; < 0: timed out
+// sweeps of concurrent fits on one device take turns (held for a whole fit)
+std::mutex& brr_sweep_lock(int dev);
+
+}  // namespace gbm

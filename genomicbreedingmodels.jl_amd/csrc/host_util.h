@@ -5,6 +5,8 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -52,7 +54,7 @@ inline std::atomic<int64_t>& alloc_counter() {
 }
 
 // When a device allocation runs out of memory, every registered trim callback frees the idle pooled
-// contexts of that device (fit_ctx.h: GBLUP fit contexts; gibbs.hip: BRR contexts, which also hold
+// contexts of that device (CtxPool below: the GBLUP fit contexts and the Gibbs samplers' contexts, which also hold
 // their captured graphs) and returns how many it freed; the allocation is then retried once.
 using TrimFn = int64_t (*)(int dev);
 struct OomTrim {
@@ -158,6 +160,72 @@ struct Stream {
   }
 };
 
+// Pooled per-device contexts of one type (FitCtx of fit_ctx.h, BrrCtx of gibbs_common.h: `dev`, a
+// `stream` and buffers that only grow). Re-entrant: a call leases a context and returns it afterwards.
+template <typename Ctx>
+class CtxPool {
+ public:
+  // never destroyed: pooled device memory must not be freed after the HIP runtime tears down
+  static CtxPool& instance() {
+    static CtxPool* p = [] {
+      auto* cp = new CtxPool;
+      // an allocation that runs out of device memory first frees the idle contexts of its device
+      // (they only grow and would otherwise hold e.g. ~50 GB each at C3's shape), then retries once
+      register_trim_hook([](int dev) { return instance().trim(dev); });
+      return cp;
+    }();
+    return *p;
+  }
+  int acquire(int dev, std::unique_ptr<Ctx>& out) {
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      auto& v = idle_[dev];
+      if (!v.empty()) {
+        out = std::move(v.back());
+        v.pop_back();
+        return GBM_OK;
+      }
+    }
+    auto c = std::make_unique<Ctx>();
+    c->dev = dev;
+    c->stream.dev = dev;
+    GBM_HIP_TRY(hipSetDevice(dev));
+    GBM_HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
+    out = std::move(c);
+    return GBM_OK;
+  }
+  void release(std::unique_ptr<Ctx> c) {
+    // nothing of this call may still run on the context's stream when another call takes it
+    (void)hipSetDevice(c->dev);
+    if (hipStreamSynchronize(c->stream.s) != hipSuccess) {
+      (void)hipGetLastError();
+      return;  // a broken context is dropped (its destructor frees what it can)
+    }
+    std::lock_guard<std::mutex> lock(mu_);
+    idle_[c->dev].push_back(std::move(c));
+  }
+  void clear() {
+    std::map<int, std::vector<std::unique_ptr<Ctx>>> drop;
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      drop.swap(idle_);
+    }
+  }
+  // drops the idle contexts of one device (their buffers are freed outside the lock); returns how many
+  int64_t trim(int dev) {
+    std::vector<std::unique_ptr<Ctx>> drop;
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      auto it = idle_.find(dev);
+      if (it != idle_.end()) drop.swap(it->second);
+    }
+    return (int64_t)drop.size();
+  }
+
+ private:
+  std::mutex mu_;
+  std::map<int, std::vector<std::unique_ptr<Ctx>>> idle_;
+};
 
 // Device list of a call. Explicit `devices` (one SNP-column shard per entry; an ordinal may
 // repeat: shards on one device are summed on that device). With none given, the calling thread

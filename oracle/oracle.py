@@ -331,7 +331,7 @@ def ridge_path_cv(X, y, folds, nlambda=100, lambda_min_ratio=0.01):
 # un-vendored and absent: restated from its published algorithm (setLT.BRR priors, sample_beta
 # single-site updates, scaled-inverse-χ² variance draws, running means every `thin` after
 # burn-in), driven by the same counter-based random numbers as the device sampler
-# (genomicbreedingmodels.jl_amd/csrc/gibbs.hip) so both follow one sample path.
+# (genomicbreedingmodels.jl_amd/csrc/gibbs_common.h) so both follow one sample path.
 # ----------------------------------------------------------------------------------------
 _U64 = (1 << 64) - 1
 

@@ -12,7 +12,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all"
 objs=()
 pids=()
-for f in stats.hip grm.hip grm_exact.hip chol.hip chol_flow.hip effects.hip gibbs.hip enet.hip pcs.hip pairscan.hip capi.cpp shard_grm.cpp dist_solve.cpp session.cpp knobs.cpp hostpack.cpp; do
+for f in stats.hip grm.hip grm_exact.hip chol.hip chol_flow.hip effects.hip gibbs_setup.hip brr.hip brr_sweep.hip bayes_abc.hip enet.hip pcs.hip pairscan.hip capi.cpp shard_grm.cpp dist_solve.cpp session.cpp knobs.cpp hostpack.cpp; do
   o="$OUT/$f.o"
   objs+=("$o")
   HO=""
