@@ -1,14 +1,22 @@
 """The elastic-net path of include/gbm.h (gbm_session_enet_path) as a literal numpy loop: one marker at a
 time, the dots taken directly from the centred columns, the same admission order, per-pass stopping rule
-and early stop as the device schedule. The checker of tests/test_lasso.py and tests/test_gpu_lasso.py
-(test infrastructure, not the product)."""
+and early stop as the device schedule. The checker of tests/test_lasso.py, tests/test_gpu_lasso.py and, through
+tests/lasso_cases.py, tests/test_gpu_lasso_edges.py (test infrastructure, not the product)."""
 import numpy as np
 
 
-def enet_path(X, y, lambdas, alpha=1.0, tol=1e-7, max_passes=1_000_000, dev_max=np.inf, fdev=0.0):
+def enet_path(X, y, lambdas, alpha=1.0, tol=1e-7, max_passes=1_000_000, dev_max=np.inf, fdev=0.0, tie=0.0):
     """Returns dict(b_path (p+1, nl_done), lambdas, dev_ratio, passes, nnz, nl_done, active (the list at the
     end, in order of admission), nactive (its length after each λ), margin (the smallest
-    | |g_j| − thr | / thr over the inactive j of every screen after the first λ), hit (max_passes reached))."""
+    | |g_j| − thr | / thr over the inactive j of every screen after the first λ), margin0 (the same over the
+    screens of the first λ, against the threshold they used), stop_margin (the smallest
+    | dmax − tol σ_y² | / (tol σ_y²) over every pass of every λ: how far the stopping rule's closest decision
+    lies from its threshold), admits (one (k, list length before, markers admitted) per non-empty admission), hit
+    (max_passes reached), first_hit (the first λ, from 0, that reached it; −1 if none)).
+
+    ``tie``: the screens of the first λ admit |g_j| > thr (1 + tie). A path that starts at λ_max itself has
+    |g_j| = thr for the marker that defines λ_max, up to the rounding of two different sums: either side is
+    the stated schedule. tie = ±1e-9 takes one side on purpose; 0 is the plain rule."""
     X = np.asarray(X, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     lambdas = np.atleast_1d(np.asarray(lambdas, dtype=np.float64))
@@ -26,7 +34,8 @@ def enet_path(X, y, lambdas, alpha=1.0, tol=1e-7, max_passes=1_000_000, dev_max=
     nl = lambdas.size
     mnl = min(5, nl)
     out_b, dev, passes_out, nnz, nact = [], [], [], [], []
-    margin, hit_any, dev_prev = np.inf, False, 0.0
+    margin, margin0, stop_margin, hit_any, dev_prev = np.inf, np.inf, np.inf, False, 0.0
+    admits, first_hit = [], -1
     for k, lam in enumerate(lambdas):
         thr = n * lam * alpha
         l2 = n * lam * (1.0 - alpha) / ys
@@ -47,20 +56,27 @@ def enet_path(X, y, lambdas, alpha=1.0, tol=1e-7, max_passes=1_000_000, dev_max=
                         b[j] = bn
                     dmax = max(dmax, x2[j] * d * d / n)
                 passes += 1
+                stop_margin = min(stop_margin, abs(dmax - tol * ys * ys) / (tol * ys * ys))
                 if dmax < tol * ys * ys:
                     break
             if hit:
                 break
             g = Xc.T @ e
             cand = ~active & (x2 > 0.0)
+            thr_s = thr * (1.0 + tie) if k == 0 else thr
             if k > 0 and cand.any():
                 margin = min(margin, np.abs(np.abs(g[cand]) - thr).min() / thr)
-            new = np.flatnonzero(cand & (np.abs(g) > thr))
+            elif cand.any():
+                margin0 = min(margin0, np.abs(np.abs(g[cand]) - thr_s).min() / thr_s)
+            new = np.flatnonzero(cand & (np.abs(g) > thr_s))
             if new.size == 0:
                 break
+            admits.append((k, len(act), int(new.size)))
             active[new] = True
             act.extend(int(j) for j in new)
         hit_any |= hit
+        if hit and first_hit < 0:
+            first_hit = k
         out_b.append(np.concatenate([[ym - mean @ b], b]))
         d = 1.0 - (e @ e) / yss
         dev.append(d)
@@ -73,7 +89,8 @@ def enet_path(X, y, lambdas, alpha=1.0, tol=1e-7, max_passes=1_000_000, dev_max=
     done = len(dev)
     return {"b_path": np.array(out_b).T, "lambdas": lambdas[:done].copy(), "dev_ratio": np.array(dev),
             "passes": np.array(passes_out), "nnz": np.array(nnz), "nl_done": done, "active": list(act),
-            "nactive": np.array(nact), "margin": margin, "hit": hit_any}
+            "nactive": np.array(nact), "margin": margin, "margin0": margin0, "stop_margin": stop_margin,
+            "admits": admits, "hit": hit_any, "first_hit": first_hit}
 
 
 def kkt_residual(X, y, lam, alpha, b):
