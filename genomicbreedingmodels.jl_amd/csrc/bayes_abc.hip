@@ -309,44 +309,47 @@ __global__ void __launch_bounds__(256) bayes_final_kernel(const double* __restri
 }
 
 }  // namespace
-}  // namespace gbm
 
-using namespace gbm;
+int bayes_check_args(const char* entry, int model, const double* X, const double* y, const double* b_hat_out, int64_t n,
+                     int64_t p, int64_t ldx, int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0,
+                     double prob_in, double counts) {
+  const std::string who(entry);
+  if (model != GBM_BAYES_A && model != GBM_BAYES_B && model != GBM_BAYES_C)
+    return fail(GBM_E_ARG, who + ": model must be GBM_BAYES_A, GBM_BAYES_B or GBM_BAYES_C");
+  GBM_TRY(gibbs_check_args(entry, X, y, b_hat_out, n, p, ldx, n_iter, n_burnin, thin, r2, df0));
+  // the gamma sampler (Marsaglia-Tsang) needs shapes >= 1: (df0 + 1)/2 of the per-marker variances
+  // and counts·prob_in, counts·(1 − prob_in) of π's Beta draw
+  if (!(df0 >= 1.0) || !(prob_in > 0.0 && prob_in < 1.0) || !(counts * prob_in >= 1.0) ||
+      !(counts * (1.0 - prob_in) >= 1.0))
+    return fail(GBM_E_ARG, who + ": bad prior (df0 >= 1, 0 < prob_in < 1, counts*prob_in >= 1, "
+                                 "counts*(1 - prob_in) >= 1)");
+  // the per-marker random streams are (iteration, marker) packed into 23 + 40 bits
+  if (n_iter > ((int64_t)1 << 23) || p >= ((int64_t)1 << 40))
+    return fail(GBM_E_ARG, who + ": n_iter <= 2^23 and p < 2^40");
+  return GBM_OK;
+}
 
-// One BayesA / BayesB / BayesC fit on a leased context (include/gbm.h gbm_bayes_fit): the shared
-// setup (genotypes, column statistics, byte quantisation, Gram blocks), then per iteration the
-// linear chain prep, μ, block 0's partial dots, one chain launch per 64-marker block, the
-// variances — captured once as a graph and replayed. Never the super-block sweep or its lock; the
-// BRR path statistics are not written.
-static int bayes_fit_impl(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
-                          int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
-                          double counts, uint64_t seed, int dev, double* b_hat_out, double* y_pred_out,
-                          double* var_out, double* pip_out) {
-  BrrLease lease;
-  GBM_TRY(CtxPool<BrrCtx>::instance().acquire(dev, lease.c));
-  BrrCtx& cx = *lease.c;
-  GBM_HIP_TRY(hipSetDevice(dev));
+int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64_t n, int64_t p, int64_t ldx,
+                const double* y, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
+                uint64_t seed, GibbsData& g, BayesState& st0) {
+  const int dev = cx.dev;
   hipStream_t s = cx.stream.s;
   const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB;
-  const int64_t nvb = (std::max(n, p) + 255) / 256;
   GBM_TRY(ensure(cx.dind, dev, 2 * p * 8));  // two copies (iteration parity), as b
   GBM_TRY(ensure(cx.dbar, dev, p * 8));
   GBM_TRY(ensure(cx.varBj, dev, p * 8));
   GBM_TRY(ensure(cx.pk, dev, ppad * 8 * 8));
-  GBM_TRY(ensure(cx.vpart, dev, nvb * 5 * 8));
-  GBM_TRY(ensure(cx.bst, dev, sizeof(BayesState)));
-  GibbsData g;
+  GBM_TRY(ensure(cx.vpart, dev, bayes_var_blocks(n, p) * 5 * 8));
   GBM_TRY(gibbs_upload(cx, X, n, p, ldx, g));
   const int64_t npad = g.npad;
-  const double xs = g.xs;
   GBM_TRY(gibbs_gram(cx, n, p, npad, nblk, 1));
   GBM_HIP_TRY(hipStreamSynchronize(s));
   GibbsPrior pr;
-  GBM_TRY(gibbs_prior("gbm_bayes_fit", y, n, p, g, pr));
+  GBM_TRY(gibbs_prior(entry, y, n, p, g, pr));
   const double shape0 = 1.1;
   double S0 = pr.vy * r2 / pr.msx * (df0 + 2.0);
   if (model != GBM_BAYES_A) S0 /= prob_in;
-  BayesState st0{};
+  st0 = BayesState{};
   st0.mu = pr.ym;
   st0.S0e = pr.vy * (1.0 - r2) * (df0 + 2.0);
   st0.varE = st0.S0e / (df0 + 2.0);
@@ -371,32 +374,73 @@ static int bayes_fit_impl(int model, const double* X, int64_t n, int64_t p, int6
   GBM_HIP_TRY(hipMemsetAsync(cx.b.p, 0, 2 * p * 8, s));
   GBM_HIP_TRY(hipMemsetAsync(cx.bbar.p, 0, p * 8, s));
   GBM_HIP_TRY(hipMemsetAsync(cx.dbar.p, 0, p * 8, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));  // init leaves scope
+  return GBM_OK;
+}
+
+void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* stp) {
+  hipStream_t s = cx.stream.s;
+  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB, npad = g.npad;
+  const double xs = g.xs;
+  const unsigned C = (unsigned)g.C64;
+  bayes_prep_kernel<<<(unsigned)(ppad / 256 + 1), 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
+                                                               (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
+                                                               (double*)cx.pk.p);
+  bayes_mu_kernel<<<1, 1024, 0, s>>>((double*)cx.e.p, n, stp);
+  gibbs_dots0(cx, n, p, g, xs > 0.0);
+  for (int64_t k = 0; k < nblk; k++) {
+    double* pin = (double*)cx.r.p + (k & 1) * (int64_t)C * BB;
+    double* pout = (double*)cx.r.p + ((k + 1) & 1) * (int64_t)C * BB;
+    if (xs > 0.0)
+      bayes_chain_kernel<uint8_t><<<C, 256, 0, s>>>((const uint8_t*)cx.D.p, npad, n, p, xs, (const double*)cx.W.p, k,
+                                                    nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
+                                                    (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+                                                    (double*)cx.e.p, stp);
+    else
+      bayes_chain_kernel<double><<<C, 256, 0, s>>>((const double*)cx.Xt.p, npad, n, p, 1.0, (const double*)cx.W.p, k,
+                                                   nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
+                                                   (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+                                                   (double*)cx.e.p, stp);
+  }
+}
+
+void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* stp) {
+  bayes_var_kernel<<<(unsigned)bayes_var_blocks(n, p), 256, 0, cx.stream.s>>>(
+      (const double*)cx.b.p, (const double*)cx.dind.p, (double*)cx.varBj.p, p, (const double*)cx.e.p, n, stp,
+      (double*)cx.vpart.p);
+}
+
+}  // namespace gbm
+
+using namespace gbm;
+
+// One BayesA / BayesB / BayesC fit on a leased context (include/gbm.h gbm_bayes_fit): the shared
+// setup (genotypes, column statistics, byte quantisation, Gram blocks), then per iteration the
+// linear chain prep, μ, block 0's partial dots, one chain launch per 64-marker block, the
+// variances — captured once as a graph and replayed. Never the super-block sweep or its lock; the
+// BRR path statistics are not written.
+static int bayes_fit_impl(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                          int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                          double counts, uint64_t seed, int dev, double* b_hat_out, double* y_pred_out,
+                          double* var_out, double* pip_out) {
+  BrrLease lease;
+  GBM_TRY(CtxPool<BrrCtx>::instance().acquire(dev, lease.c));
+  BrrCtx& cx = *lease.c;
+  GBM_HIP_TRY(hipSetDevice(dev));
+  hipStream_t s = cx.stream.s;
+  GBM_TRY(ensure(cx.bst, dev, sizeof(BayesState)));
+  GibbsData g;
+  BayesState st0{};
+  GBM_TRY(bayes_setup("gbm_bayes_fit", cx, model, X, n, p, ldx, y, n_burnin, thin, r2, df0, prob_in, counts, seed, g,
+                      st0));
+  const int64_t npad = g.npad, nvb = bayes_var_blocks(n, p);
+  const double xs = g.xs;
   GBM_HIP_TRY(hipMemcpyAsync(cx.bst.p, &st0, sizeof(BayesState), hipMemcpyHostToDevice, s));
   GBM_HIP_TRY(hipStreamSynchronize(s));
   auto* stp = (BayesState*)cx.bst.p;
-  const unsigned C = (unsigned)g.C64;
   auto enqueue_iteration = [&]() -> int {
-    bayes_prep_kernel<<<(unsigned)(ppad / 256 + 1), 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
-                                                                 (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
-                                                                 (double*)cx.pk.p);
-    bayes_mu_kernel<<<1, 1024, 0, s>>>((double*)cx.e.p, n, stp);
-    gibbs_dots0(cx, n, p, g, xs > 0.0);
-    for (int64_t k = 0; k < nblk; k++) {
-      double* pin = (double*)cx.r.p + (k & 1) * (int64_t)C * BB;
-      double* pout = (double*)cx.r.p + ((k + 1) & 1) * (int64_t)C * BB;
-      if (xs > 0.0)
-        bayes_chain_kernel<uint8_t><<<C, 256, 0, s>>>((const uint8_t*)cx.D.p, npad, n, p, xs, (const double*)cx.W.p, k,
-                                                      nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
-                                                      (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
-                                                      (double*)cx.e.p, stp);
-      else
-        bayes_chain_kernel<double><<<C, 256, 0, s>>>((const double*)cx.Xt.p, npad, n, p, 1.0, (const double*)cx.W.p, k,
-                                                     nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
-                                                     (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
-                                                     (double*)cx.e.p, stp);
-    }
-    bayes_var_kernel<<<(unsigned)nvb, 256, 0, s>>>((const double*)cx.b.p, (const double*)cx.dind.p, (double*)cx.varBj.p, p,
-                                                   (const double*)cx.e.p, n, stp, (double*)cx.vpart.p);
+    bayes_enqueue_chain(cx, n, p, g, stp);
+    bayes_enqueue_var(cx, n, p, stp);
     bayes_final_kernel<<<1, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp);
     return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, "gbm_bayes_fit: launch failed");
   };
@@ -421,20 +465,11 @@ extern "C" int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, i
                              double* var_out, double* pip_out) {
   RoctxRange r_("gbm_bayes_fit");
   set_error("");
-  if (model != GBM_BAYES_A && model != GBM_BAYES_B && model != GBM_BAYES_C)
-    return fail(GBM_E_ARG, "gbm_bayes_fit: model must be GBM_BAYES_A, GBM_BAYES_B or GBM_BAYES_C");
-  GBM_TRY(gibbs_check_args("gbm_bayes_fit", X, y, b_hat_out, n, p, ldx, n_iter, n_burnin, thin, r2, df0));
-  // the gamma sampler (Marsaglia-Tsang) needs shapes >= 1: (df0 + 1)/2 of the per-marker variances
-  // and counts·prob_in, counts·(1 − prob_in) of π's Beta draw
-  if (!(df0 >= 1.0) || !(prob_in > 0.0 && prob_in < 1.0) || !(counts * prob_in >= 1.0) ||
-      !(counts * (1.0 - prob_in) >= 1.0))
-    return fail(GBM_E_ARG, "gbm_bayes_fit: bad prior (df0 >= 1, 0 < prob_in < 1, counts*prob_in >= 1, "
-                           "counts*(1 - prob_in) >= 1)");
-  // the per-marker random streams are (iteration, marker) packed into 23 + 40 bits
-  if (n_iter > ((int64_t)1 << 23) || p >= ((int64_t)1 << 40))
-    return fail(GBM_E_ARG, "gbm_bayes_fit: n_iter <= 2^23 and p < 2^40");
+  GBM_TRY(bayes_check_args("gbm_bayes_fit", model, X, y, b_hat_out, n, p, ldx, n_iter, n_burnin, thin, r2, df0, prob_in,
+                           counts));
   int dev = 0;
   GBM_TRY(gibbs_check_run("gbm_bayes_fit", y, n, n_iter, n_burnin, thin, device, dev));
   return bayes_fit_impl(model, X, n, p, ldx, y, n_iter, n_burnin, thin, r2, df0, prob_in, counts, seed, dev, b_hat_out,
                         y_pred_out, var_out, pip_out);
 }
+

@@ -2,7 +2,8 @@
 //   gibbs_setup.hip  the kernels, pooled context and host steps both samplers use;
 //   brr.hip          Bayesian ridge regression: the per-launch kernels, gbm_brr_fit, the debug exports;
 //   brr_sweep.hip    its persistent super-block sweep, behind brr_sweep_plan / _setup / _enqueue;
-//   bayes_abc.hip    BayesA, BayesB, BayesC: gbm_bayes_fit.
+//   bayes_abc.hip    BayesA, BayesB, BayesC: gbm_bayes_fit, and the steps the ordinal fit replays;
+//   bayes_ordinal.hip  their ordinal (threshold-model) response: gbm_bayes_fit_ordinal.
 //
 // Random numbers: a counter-based hash of (seed, stream, counter) (no sampler state), Box-Muller
 // normals and Marsaglia-Tsang gammas, restated bit-for-bit in oracle/oracle.py (brr_*), so the
@@ -24,7 +25,7 @@ constexpr int BK2 = 2 * BB;  // markers per launch of the byte per-launch path
 constexpr int SBK = 512;  // markers per super-block (brr_sweep.hip)
 constexpr int SBN = SBK / (2 * BB);  // 128-marker sub-blocks per super-block
 
-__device__ __forceinline__ double brr_u01(uint64_t seed, uint64_t a, uint64_t b) {
+__host__ __device__ __forceinline__ double brr_u01(uint64_t seed, uint64_t a, uint64_t b) {
   const uint64_t h = mix64(mix64(seed ^ (a * 0xD1B54A32D192ED03ull)) ^ (b * 0x8CB92BA72F3D8DD7ull));
   return ((double)(h >> 11) + 0.5) * 0x1.0p-53;
 }
@@ -47,6 +48,76 @@ __device__ inline double brr_chisq(uint64_t seed, uint64_t a, double df) {
   return df;  // unreachable in practice (acceptance ≈ 0.98 per attempt)
 }
 
+// ---- the ordinal response's truncated normal (bayes_ordinal.hip; include/gbm.h gbm_bayes_fit_ordinal) ----
+// Φ(x) = ½ erfc(−x/√2): 0 at −∞, 1 at +∞
+__host__ __device__ inline double gibbs_phi(double x) { return 0.5 * erfc(-x * 0.7071067811865476); }
+// Φ⁻¹(p) in fp64: Wichura's algorithm AS241, routine PPND16 (Applied Statistics 37 (1988) 477-484),
+// written out here so that the host's start draws, the device's and tests/ordinal_ref.py's restatement
+// run the same operations. p = 0 gives −∞, p = 1 gives +∞.
+__host__ __device__ inline double gibbs_ppnd16(double p) {
+  const double q = p - 0.5;
+  if (fabs(q) <= 0.425) {
+    const double r = 0.180625 - q * q;
+    const double num =
+        ((((((r * 2509.0809287301226727 + 33430.575583588128105) * r + 67265.770927008700853) * r +
+            45921.953931549871457) * r + 13731.693765509461125) * r + 1971.5909503065514427) * r +
+         133.14166789178437745) * r + 3.387132872796366608;
+    const double den =
+        ((((((r * 5226.495278852854561 + 28729.085735721942674) * r + 39307.89580009271061) * r +
+            21213.794301586595867) * r + 5394.1960214247511077) * r + 687.1870074920579083) * r +
+         42.313330701600911252) * r + 1.0;
+    return q * num / den;
+  }
+  double r = sqrt(-log(q < 0.0 ? p : 1.0 - p));
+  double val;
+  if (r <= 5.0) {
+    r -= 1.6;
+    const double num =
+        ((((((r * 7.7454501427834140764e-4 + 0.0227238449892691845833) * r + 0.24178072517745061177) * r +
+            1.27045825245236838258) * r + 3.64784832476320460504) * r + 5.7694972214606914055) * r +
+         4.6303378461565452959) * r + 1.42343711074968357734;
+    const double den =
+        ((((((r * 1.05075007164441684324e-9 + 5.475938084995344946e-4) * r + 0.0151986665636164571966) * r +
+            0.14810397642748007459) * r + 0.68976733498510000455) * r + 1.6763848301838038494) * r +
+         2.05319162663775882187) * r + 1.0;
+    val = num / den;
+  } else {
+    r -= 5.0;
+    const double num =
+        ((((((r * 2.01033439929228813265e-7 + 2.71155556874348757815e-5) * r + 0.0012426609473880784386) * r +
+            0.026532189526576123093) * r + 0.29656057182850489123) * r + 1.7848265399172913358) * r +
+         5.4637849111641143699) * r + 6.6579046435011037772;
+    const double den =
+        ((((((r * 2.04426310338993978564e-15 + 1.4215117583164458887e-7) * r + 1.8463183175100546818e-5) * r +
+            7.868691311456132591e-4) * r + 0.0148753612908506148525) * r + 0.13692988092273580531) * r +
+         0.59983220655588793769) * r + 1.0;
+    val = num / den;
+  }
+  return q < 0.0 ? -val : val;
+}
+// TN(m; a, b; u): the N(m, 1) variate truncated to [a, b] (a < b, at most one of them infinite) by inverse CDF
+// from one uniform u, worked in the tail below the mean (an interval above it is reflected), where Φ keeps
+// its relative precision.
+__host__ __device__ inline double gibbs_truncnorm(double m, double a, double b, double u) {
+  double al = a - m, be = b - m;
+  const bool refl = al >= 0.0;
+  if (refl) {
+    const double t = al;
+    al = -be;
+    be = -t;
+  }
+  const double pa = gibbs_phi(al), w = gibbs_phi(be) - pa;
+  double x;
+  if (w > 0.0) {
+    x = gibbs_ppnd16(pa + u * w);
+    x = x < al ? al : x;
+    x = x > be ? be : x;
+  } else {
+    x = fabs(be) <= fabs(al) ? be : al;  // no mass in fp64: the end nearer the mean (finite)
+  }
+  return refl ? m - x : m + x;
+}
+
 struct BrrState {
   double mu, varE, varB, S0e, S0b, df0e, df0b;
   double mubar, varEbar, varBbar;
@@ -61,6 +132,14 @@ struct BayesState {
   int64_t it, burnin, thin, nsum;
   uint64_t seed;
   int model;  // GBM_BAYES_A, _B or _C
+};
+// gbm_bayes_fit_ordinal: the chain's state (varE stays 1) and the thresholds of K classes
+constexpr int ORD_MAXK = 32;
+struct OrdinalState {
+  BayesState s;
+  double t[ORD_MAXK + 1];     // t_0 = −∞ < t_1 < … < t_{K−1} < t_K = +∞
+  double tbar[ORD_MAXK + 1];  // running means of t_1 … t_{K−1} (entry k)
+  int64_t K;
 };
 // the sample gate: does this iteration enter the running posterior means?
 template <typename State>
@@ -204,7 +283,7 @@ inline int64_t key_of(const DevBuf& b) { return (int64_t)(uintptr_t)b.p; }  // a
 // Pooled per-device sampler contexts (as fit_ctx.h pools the GBLUP fit contexts): a fit leases one,
 // its buffers only grow, so repeated fits of one shape allocate no device memory after the first
 // (cvmultithread! runs bayesian("BRR") once per fold). BRR and BayesA/B/C fits that alternate on
-// one context keep both captured graphs.
+// one context keep both captured graphs; the ordinal fits have a third.
 struct BrrCtx {
   int dev = 0;
   Stream stream;
@@ -213,11 +292,13 @@ struct BrrCtx {
   DevBuf CS, CS2;                          // its cross-Grams C_s = X_sᵀ X_{s−1}, C2_s = X_sᵀ X_{s−2}
   DevBuf trace;                            // GBM_BRR_TRACE timestamps of this context's last sweep
   DevBuf dind, dbar, varBj, pk, vpart, bst;  // gbm_bayes_fit: indicators, PIP, varB_j, step constants, partial sums, state
-  IterGraph brr_graph, bayes_graph;
+  DevBuf oys, oyh, ocls, opart, oprob, ost;  // gbm_bayes_fit_ordinal: y*, ŷ, classes, min/max partials, P(class), state
+  IterGraph brr_graph, bayes_graph, ordinal_graph;
   ~BrrCtx() {
     (void)hipSetDevice(dev);
     brr_graph.drop();
     bayes_graph.drop();
+    ordinal_graph.drop();
   }
 };
 struct BrrLease {
@@ -257,6 +338,23 @@ int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const 
 // the host, b_hat_out[0] = *mubar (a field of fin), then the optional y_pred = μ̄ + X b̄.
 int gibbs_outputs(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, const DevBuf& state, void* fin, size_t fin_bytes,
                   const double* mubar, double* b_hat_out, double* pip_out, double* y_pred_out);
+
+// ---- what gbm_bayes_fit shares with gbm_bayes_fit_ordinal (bayes_abc.hip) -------------------------
+// gbm_bayes_fit's argument checks in front of gibbs_check_run (`entry` opens the error text)
+int bayes_check_args(const char* entry, int model, const double* X, const double* y, const double* b_hat_out, int64_t n,
+                     int64_t p, int64_t ldx, int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0,
+                     double prob_in, double counts);
+// A fit's setup on its context: genotypes, Gram blocks, the prior moments of y, the start state st0 (not
+// uploaded: the caller owns the state's buffer) and the start values of e, b, d, varB_j and the running means.
+int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64_t n, int64_t p, int64_t ldx,
+                const double* y, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
+                uint64_t seed, GibbsData& g, BayesState& st0);
+// steps 1 and 2 of an iteration on the state st: the step constants, μ, block 0's partial dots, one chain
+// launch per 64-marker block
+void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* st);
+// step 3's per-marker variances and the partial sums of the scalar draws (vpart)
+void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* st);
+inline int64_t bayes_var_blocks(int64_t n, int64_t p) { return (std::max(n, p) + 255) / 256; }
 
 // ---- the super-block sweep's host interface (brr_sweep.hip) -----------------------------------------
 // The chunk shape of a sweep over n individuals on a device of `cus` CUs, per the knobs

@@ -3,9 +3,13 @@ ridge regression), with the Gibbs sampler on the GPU (libgbm ``gbm_brr_fit``) in
 Rscript/BGLR round trip (src/bayes.jl:28-105). SURVEY.md §8f row 3, config C4.
 
 ``bayesa``, ``bayesb``, ``bayesc`` — mirrors of the reference's model functions
-(src/linear.jl:440-626) over the BayesA / BayesB / BayesC samplers of libgbm ``gbm_bayes_fit``."""
+(src/linear.jl:440-626) over the BayesA / BayesB / BayesC samplers of libgbm ``gbm_bayes_fit``.
+
+``bayesian(m, ..., response_type="ordinal")`` and ``bayes_ordinal_arrays`` — the same three models with the
+reference's ordinal response (the threshold model of libgbm ``gbm_bayes_fit_ordinal``)."""
 from __future__ import annotations
 
+import ctypes
 import warnings
 
 import numpy as np
@@ -18,6 +22,7 @@ from .types import Fit, Genomes, Phenomes
 
 SUPPORTED = ("BRR",)
 BAYES_MODELS = {"BayesA": 1, "BayesB": 2, "BayesC": 3}  # include/gbm.h GBM_BAYES_*
+RESPONSE_TYPES = ("gaussian", "ordinal")  # the reference's (src/bayes.jl:32)
 
 
 def brr_arrays(X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500, thin: int = 5,
@@ -44,13 +49,22 @@ def bayesian(bglr_model: str = "BRR", *, genomes: Genomes, phenomes: Phenomes, i
              idx_loci_alleles=None, idx_trait: int = 1, response_type: str = "gaussian", n_burnin: int = 500,
              n_iter: int = 1500, verbose: bool = False, thin: int = 5, seed: int = 42, device: int = 0) -> Fit:
     """Bayesian genomic prediction, same signature and Fit assembly as the reference
-    (src/bayes.jl:158-224). Only the Gaussian BRR model runs here; BayesA, BayesB and BayesC run
-    through the model functions ``bayesa``, ``bayesb`` and ``bayesc``."""
+    (src/bayes.jl:158-224). With the Gaussian response only the BRR model runs here; BayesA, BayesB
+    and BayesC run through the model functions ``bayesa``, ``bayesb`` and ``bayesc``. With
+    ``response_type="ordinal"`` (the threshold model, ``gbm_bayes_fit_ordinal``) the model is BayesA,
+    BayesB or BayesC: ``y_true`` holds the observed classes and ``y_pred`` the liability μ̄ + X b̄
+    (the reference's ``X * b_hat``)."""
+    if response_type not in RESPONSE_TYPES:
+        raise ArgumentError(f"response_type `{response_type}` is not one of {RESPONSE_TYPES}")
+    if response_type == "ordinal":
+        if bglr_model not in BAYES_MODELS:
+            raise ArgumentError(f"bglr_model `{bglr_model}` has no ordinal response; supported with "
+                                f"response_type = 'ordinal': {tuple(BAYES_MODELS)}")
+        return _ordinal_fit(bglr_model, genomes, phenomes, idx_entries, idx_loci_alleles, idx_trait, n_iter, n_burnin,
+                            thin, seed, device, verbose)
     if bglr_model not in SUPPORTED:
         hint = "; use gbm.bayesa, gbm.bayesb or gbm.bayesc for BayesA, BayesB, BayesC" if bglr_model in BAYES_MODELS else ""
         raise ArgumentError(f"bglr_model `{bglr_model}` is not available through bayesian(); supported: {SUPPORTED}{hint}")
-    if response_type != "gaussian":
-        raise ArgumentError("only response_type = 'gaussian' is supported")
     X, y, entries, populations, loci_alleles = extractxyetc(
         genomes, phenomes, idx_entries=idx_entries, idx_loci_alleles=idx_loci_alleles, idx_trait=idx_trait,
         add_intercept=False)
@@ -93,6 +107,64 @@ def bayes_arrays(model: str, X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500
                            _lib.ptr(var), _lib.ptr(pip))
     _lib.check(rc, "gbm_bayes_fit")
     return b_hat, y_pred, var, pip
+
+
+def bayes_ordinal_arrays(model: str, X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500,
+                         thin: int = 5, r2: float = 0.5, df0: float = 5.0, prob_in: float = 0.5, counts: float = 10.0,
+                         seed: int = 42, device: int = 0, probs: bool = True):
+    """Array-level BayesA / BayesB / BayesC Gibbs sampler with an ordinal response (the threshold model of
+    ``gbm_bayes_fit_ordinal``): the classes are the sorted distinct values of ``y`` (2 to 32 of them).
+    Returns (b_hat (p+1,), y_pred (n,) the liability μ̄ + X b̄, [1, mean_j σ²_b_j, π] posterior means, pip (p,),
+    classes (K,), thresholds (K−1,) posterior means of the finite thresholds, probs (n, K) posterior means of
+    P(class k | individual i), or None with ``probs=False``)."""
+    if model not in BAYES_MODELS:
+        raise ArgumentError(f"model `{model}` is not one of {tuple(BAYES_MODELS)}")
+    X = np.asfortranarray(np.asarray(X, dtype=np.float64))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    n, p = X.shape
+    K = len(np.unique(y))
+    b_hat = np.zeros(p + 1)
+    y_pred = np.zeros(n)
+    var = np.zeros(3)
+    pip = np.zeros(p)
+    classes = np.zeros(max(K, 1))
+    thresholds = np.zeros(max(K - 1, 1))
+    pr = np.zeros((n, K), order="F") if probs else None
+    nclass = ctypes.c_int64(0)
+    lib = _lib.load()
+    rc = lib.gbm_bayes_fit_ordinal(BAYES_MODELS[model], _lib.ptr(X), n, p, n, _lib.ptr(y), int(n_iter), int(n_burnin),
+                                   int(thin), float(r2), float(df0), float(prob_in), float(counts),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(device), _lib.ptr(b_hat), _lib.ptr(y_pred),
+                                   _lib.ptr(var), _lib.ptr(pip), max(K, 1), ctypes.addressof(nclass),
+                                   _lib.ptr(classes), _lib.ptr(thresholds), _lib.ptr(pr), n)
+    _lib.check(rc, "gbm_bayes_fit_ordinal")
+    return b_hat, y_pred, var, pip, classes[:nclass.value], thresholds[:nclass.value - 1], pr
+
+
+def _ordinal_fit(model: str, genomes: Genomes, phenomes: Phenomes, idx_entries, idx_loci_alleles, idx_trait: int,
+                 n_iter: int, n_burnin: int, thin: int, seed: int, device: int, verbose: bool) -> Fit:
+    """Fit assembly of ``bayesian`` (src/bayes.jl:158-224) for the ordinal response."""
+    X, y, entries, populations, loci_alleles = extractxyetc(
+        genomes, phenomes, idx_entries=idx_entries, idx_loci_alleles=idx_loci_alleles, idx_trait=idx_trait,
+        add_intercept=False)
+    fit = Fit(n=X.shape[0], l=X.shape[1] + 1)
+    fit.model = model
+    fit.b_hat_labels = ["intercept"] + list(loci_alleles)
+    fit.trait = phenomes.traits[idx_trait - 1]
+    fit.entries = entries
+    fit.populations = populations
+    fit.y_true = y
+    b_hat, y_pred, var, pip, classes, thresholds, _ = bayes_ordinal_arrays(
+        model, X, y, n_iter=n_iter, n_burnin=n_burnin, thin=thin, seed=seed, device=device, probs=False)
+    fit.b_hat = b_hat
+    fit.y_pred = y_pred
+    fit.metrics = metrics(y, y_pred)
+    if verbose:
+        print(fit.metrics, "classes", classes, "posterior means: thresholds", thresholds, "mean varB", var[1], "pi",
+              var[2], "mean PIP", pip.mean())
+    if not fit.checkdims():
+        raise GBMError("Error fitting " + fit.model + ".")
+    return fit
 
 
 def _bayes_model_function(model: str, genomes: Genomes, phenomes: Phenomes, idx_entries, idx_loci_alleles,

@@ -13,7 +13,8 @@ from ._lib import ArgumentError, GBMError
 from .types import Fit, Genomes, Phenomes
 
 # src/prediction.jl:225 plus the new "gblup" (SURVEY.md §8b decision)
-LINEAR_MODELS = ("ols", "ridge", "lasso", "bayesa", "bayesb", "bayesc", "gblup", "BRR")
+LINEAR_MODELS = ("ols", "ridge", "lasso", "bayesa", "bayesb", "bayesc", "gblup", "BRR",
+                 "BayesA", "BayesB", "BayesC")  # the last three: bayesian(..., response_type="ordinal"), the liability
 
 
 def extractxyetc(genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None,

@@ -160,17 +160,38 @@ const GBM_BAYES_MODELS = Dict("BayesA" => Cint(1), "BayesB" => Cint(2), "BayesC"
 `bglr`'s keyword signature (src/bayes.jl:28-36) over `gbm_bayes_fit`: returns `[posterior mean μ;
 posterior means of the marker effects d_j b_j]`, the vector `bglr` reads back from
 `c(sol\$mu, sol\$ETA\$MRK\$b)` (src/bayes.jl:83-104), so `bayesian` — and through it `bayesa`,
-`bayesb`, `bayesc` — uses it unchanged. Gaussian response only; BGLR's default priors
-(df0 = 5, R2 = 0.5, probIn = 0.5, counts = 10).
+`bayesb`, `bayesc` — uses it unchanged. `response_type = "ordinal"` runs the threshold model of
+`gbm_bayes_fit_ordinal` on the sorted distinct values of `y` (2 to 32 classes); the vector returned then
+predicts the liability, as BGLR's. BGLR's default priors (df0 = 5, R2 = 0.5, probIn = 0.5, counts = 10).
+(The ordinal `ccall` has not been run: no Julia where this was written; its argument list is include/gbm.h's.)
 """
 function bglr_gpu(; G::Matrix{Float64}, y::Vector{Float64}, model::String = "BayesA",
                   response_type::String = "gaussian", n_iter::Int64 = 1_500, n_burnin::Int64 = 500,
                   verbose::Bool = false, thin::Int64 = 5, seed::UInt64 = UInt64(42), device::Integer = 0)
     haskey(GBM_BAYES_MODELS, model) || throw(ArgumentError("bglr_gpu: model `$model` is not BayesA, BayesB or BayesC"))
-    response_type == "gaussian" || throw(ArgumentError("bglr_gpu: only response_type = \"gaussian\" runs on the GPU"))
+    response_type in ("gaussian", "ordinal") ||
+        throw(ArgumentError("bglr_gpu: response_type `$response_type` is not \"gaussian\" or \"ordinal\""))
     n, p = size(G)
     b_hat = zeros(p + 1)
     var = zeros(3)
+    if response_type == "ordinal"
+        max_classes = 32
+        nclass = Ref{Int64}(0)
+        classes = zeros(max_classes)
+        thresholds = zeros(max_classes - 1)
+        GC.@preserve G y b_hat var classes thresholds begin
+            rc = ccall((:gbm_bayes_fit_ordinal, LIBGBM), Cint,
+                       (Cint, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64,
+                        Float64, Float64, UInt64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Int64, Ref{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                       GBM_BAYES_MODELS[model], G, n, p, stride(G, 2), y, n_iter, n_burnin, thin, 0.5, 5.0, 0.5, 10.0,
+                       seed, device, b_hat, C_NULL, var, C_NULL, max_classes, nclass, classes, thresholds, C_NULL, n)
+        end
+        gbm_check(rc, "bglr_gpu")
+        verbose && @info "bglr_gpu posterior means (ordinal)" model classes = classes[1:nclass[]] thresholds =
+            thresholds[1:(nclass[] - 1)] mean_varB = var[2] pi = var[3]
+        return b_hat
+    end
     GC.@preserve G y b_hat var begin
         rc = ccall((:gbm_bayes_fit, LIBGBM), Cint,
                    (Cint, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64,

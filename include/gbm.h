@@ -741,6 +741,50 @@ int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx,
                   double* y_pred_out /* n, may be NULL */, double* var_out /* 3; may be NULL */,
                   double* pip_out /* p, may be NULL */);
 
+/*
+ * ---- BayesA, BayesB and BayesC with an ordinal response (threshold model) -------------------
+ * The reference's bayesian(...; response_type = "ordinal") (src/bayes.jl:28-36, 161-172): BGLR's
+ * probit threshold model as restated here (BGLR is not vendored: parity with BGLR itself is
+ * unpinned). It is gbm_bayes_fit's chain on a latent liability y* with the residual variance fixed
+ * at 1. (Additive: GBM_VERSION stays 212.)
+ *
+ * Classes and start thresholds: the K classes are the distinct values of y in sorted order
+ *   (2 <= K <= 32), z_i in {0 … K−1} the class of individual i; t_0 = −∞, t_K = +∞ and, with cum_k the
+ *   number of individuals in the classes below k, t_k = Φ⁻¹(cum_k/n) for k = 1 … K−1. y*_i lies in
+ *   [t_{z_i}, t_{z_i+1}]. varE ≡ 1 is never drawn.
+ * Truncated normal TN(m; a, b; u), by inverse CDF from one uniform u: α = a − m, β = b − m; if α >= 0
+ *   reflect, (α, β) ← (−β, −α); pa = Φ(α), pb = Φ(β); x = Φ⁻¹(pa + u (pb − pa)) clamped to [α, β], or,
+ *   when pb − pa is not > 0, the end of [α, β] nearer 0; the result is m − x after a reflection, else
+ *   m + x. Φ(x) = erfc(−x/√2)/2 (0 at −∞, 1 at +∞); Φ⁻¹ is Wichura's AS241 PPND16 in fp64, the library's
+ *   own routine (csrc/gibbs_common.h).
+ * Start: y*_i = TN(0; t_{z_i}, t_{z_i+1}; u01(seed, 2^64 − 1, i)); vy = var(y*) (ddof 1), μ = mean(y*),
+ *   e = y* − μ; every other start value and prior quantity as gbm_bayes_fit's from this vy (S0e is
+ *   unused), varE = 1.
+ * One iteration `it` (A = 8 it): steps 1 and 2 of gbm_bayes_fit unchanged, with varE = 1; then
+ *   (a) for every i: ŷ_i = y*_i − e_i, y*_i = TN(ŷ_i; t_{z_i}, t_{z_i+1}; u01(seed, A+7, i)),
+ *       e_i = y*_i − ŷ_i;
+ *   (b) for m = 2 … K−1 in order: lo = max(max{y*_i : z_i = m−1}, t_{m−1}) (t_{m−1} as just updated),
+ *       hi = min(min{y*_i : z_i = m}, t_{m+1}), t_m = lo + (hi − lo) u01(seed, A+7, 0xFFFFFFFF00000000 + m);
+ *       t_1 never moves (it identifies μ);
+ *   (c) when the iteration is sampled (step 4's gate): running means of t_1 … t_{K−1} and of
+ *       P(class k | i) = Φ(t_{k+1} − ŷ_i) − Φ(t_k − ŷ_i), with the ŷ_i of (a) and the thresholds of (b);
+ *   then step 3 without the draw of varE (the stream A+2 stays unused) and step 4.
+ * b_hat_out, y_pred_out (the liability b0 + X b), pip_out as gbm_bayes_fit; var_out (3, optional) =
+ * [1, mean of mean_j varB_j, mean of π]. *nclass_out = K; classes_out (max_classes) receives the K
+ * class values; thresholds_out (max_classes − 1; may be NULL) the posterior means of t_1 … t_{K−1};
+ * probs_out (may be NULL; n x K column-major, column pitch ldprobs >= n) the posterior means of
+ * P(class k | i). GBM_E_ARG, before any device work: gbm_bayes_fit's own checks, K < 2, K > 32,
+ * K > max_classes, NaN/Inf in y, n >= 2^32. Genotype storage as gbm_bayes_fit.
+ */
+int gbm_bayes_fit_ordinal(int model, const double* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                          int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in,
+                          double counts, uint64_t seed, int device, double* b_hat_out /* p+1 */,
+                          double* y_pred_out /* n, may be NULL */, double* var_out /* 3; may be NULL */,
+                          double* pip_out /* p, may be NULL */, int64_t max_classes, int64_t* nclass_out,
+                          double* classes_out /* max_classes */,
+                          double* thresholds_out /* max_classes - 1; may be NULL */,
+                          double* probs_out /* n x K, may be NULL */, int64_t ldprobs);
+
 /* --------------------------------------------------------------------------------------
  * Diagnostics (tests and timing tools; no reference counterpart).
  * ------------------------------------------------------------------------------------ */
