@@ -1,5 +1,5 @@
 // Lasso / elastic-net paths by cyclic coordinate descent on an active set — DESIGN.md §4.10; the
-// device side of gbm_session_enet_path (session.cpp), which replaces the GLMNet.glmnetcv(alpha = 1)
+// device side of gbm_session_enet_path (session_linear.cpp), which replaces the GLMNet.glmnetcv(alpha = 1)
 // call of reference lasso (src/linear.jl:333-343).
 //
 // The active markers' centred rows are packed in admission order into Za (A x lda fp64 locus rows,

@@ -194,7 +194,7 @@ int launch_pair_scan(int op, const double* W, int64_t ldw, int64_t n, int64_t l,
 int launch_pair_select(const double* beta, int64_t m, int64_t base, double eps, int64_t k, void* state, int64_t* blk,
                        int64_t* cand_idx, double* cand_beta, hipStream_t s);
 
-// REML choice of λ (session.cpp; reference loglikreml src/gwas.jl:450-483 with X = 1)
+// REML choice of λ (session_reml.cpp; reference loglikreml src/gwas.jl:450-483 with X = 1)
 struct RemlEval {
   double g, s2u, s2e;  // objective, σ²_u, σ²_e at one λ (σ²_u profiled inside the box [eps, 1]²)
 };

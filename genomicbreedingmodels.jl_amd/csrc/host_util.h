@@ -1,6 +1,6 @@
 // Host-side helpers shared by the libgbm entry points (capi.cpp, shard_grm.cpp and dist_solve.cpp
-// through fit_ctx.h; session.cpp): RAII device buffers and streams, device-list and phenotype
-// validation. Not part of the ABI.
+// through fit_ctx.h; session.cpp and session_*.cpp through session.h): RAII device buffers and
+// streams, device-list and phenotype validation. Not part of the ABI.
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -34,6 +34,10 @@ struct DevMem {
   DevMem(const DevMem&) = delete;
   DevMem& operator=(const DevMem&) = delete;
   ~DevMem() { reset(); }
+  template <class T>
+  T* as() const {  // the buffer as an array of T (T may be const)
+    return static_cast<T*>(p);
+  }
   void reset() {
     if (p) {
       int cur = 0;

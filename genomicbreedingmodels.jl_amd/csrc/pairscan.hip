@@ -1,5 +1,5 @@
-// Kernels of the epistasis feature scan (driver: gbm_session_pair_scan, session.cpp): the slope of
-// the simple regression y ~ [1, f(x_i, x_j)] for every ordered pair of loci (reference transform2,
+// Kernels of the epistasis feature scan (driver: gbm_session_pair_scan, session_pairscan.cpp): the
+// slope of the simple regression y ~ [1, f(x_i, x_j)] for every ordered pair of loci (reference transform2,
 // src/transformation.jl:319-468) or f(x_j) for every locus (transform1, :130-238), and the K largest |slope|.
 //
 //   pair_prep_kernel   gathers the training rows and the chosen loci of the resident Xt into the compact

@@ -1,4 +1,4 @@
-// Kernels of the block eigensolver on a session's cached GRM (driver: gbm_session_pcs, session.cpp; DESIGN.md
+// Kernels of the block eigensolver on a session's cached GRM (driver: gbm_session_pcs, session_pcs.cpp; DESIGN.md
 // §4.11): the symmetric fill of K from the GRM's defined elements, the skinny product Yt = Qt·K on fp64 MFMA, and
 // the small per-iteration kernels (Gram products, 32x32 row transforms, Ritz residuals, the reference operator's
 // rank-one corrections, column statistics, traces, the start block).

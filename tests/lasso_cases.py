@@ -155,7 +155,7 @@ def gram_slices(n):
 
 
 def cap(n, p):
-    """Rows of the packed active set (session.cpp): min(p, 2 npad), npad = n rounded up to 128."""
+    """Rows of the packed active set (session_linear.cpp): min(p, 2 npad), npad = n rounded up to 128."""
     return min(p, 2 * (-(-n // 128) * 128))
 
 

@@ -1,5 +1,5 @@
 // Host-side driver for the AddressSanitizer / UndefinedBehaviorSanitizer build of libgbm's host
-// shim (capi.cpp, session.cpp and the .hip files' launchers): it calls every C-ABI entry point a
+// shim (capi.cpp, session*.cpp and the .hip files' launchers): it calls every C-ABI entry point a
 // binding uses, with bad arguments and (on a machine without a GPU) on the no-device paths, from
 // one thread and from eight at once (the reference's cvmultithread! calls the model function from
 // Threads.@threads), and checks return codes and the thread-local error strings. Memory errors

@@ -81,7 +81,7 @@ def test_gblup_model_recognition():
 
 def test_reml_profile_algebra_matches_loglikreml():
     """libgbm evaluates loglikreml from one Cholesky of G + λI: logdet, 1ᵀV⁻¹1, 1ᵀV⁻¹y, yᵀV⁻¹y
-    (session.cpp reml_objective). Check that algebra against the pinv restatement."""
+    (session_reml.cpp reml_objective). Check that algebra against the pinv restatement."""
     X = oracle.synth_genotypes(9, 80, 300)
     y = oracle.synth_phenotypes(X, 10)[:, 0]
     G, _ = oracle.grm(X)

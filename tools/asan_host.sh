@@ -1,5 +1,5 @@
 # AddressSanitizer + UndefinedBehaviorSanitizer build of libgbm's HOST code (the C-ABI shim
-# capi.cpp / session.cpp and the host launchers in the .hip files; device code is built as usual:
+# capi.cpp / session*.cpp and the host launchers in the .hip files; device code is built as usual:
 # GPU sanitizers are not used on this pool) linked into tests/native/asan_driver.cpp and
 # tests/native/asan_pcs_driver.cpp and tests/native/asan_ordinal_driver.cpp, then run.
 # CPU only: the drivers exercise argument validation, the no-device paths and thread-local errors.
@@ -12,7 +12,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all"
 objs=()
 pids=()
-for f in stats.hip grm.hip grm_exact.hip chol.hip chol_flow.hip effects.hip gibbs_setup.hip brr.hip brr_sweep.hip bayes_abc.hip bayes_ordinal.hip enet.hip pcs.hip pairscan.hip capi.cpp shard_grm.cpp dist_solve.cpp session.cpp knobs.cpp hostpack.cpp; do
+for f in stats.hip grm.hip grm_exact.hip chol.hip chol_flow.hip effects.hip gibbs_setup.hip brr.hip brr_sweep.hip bayes_abc.hip bayes_ordinal.hip enet.hip pcs.hip pairscan.hip capi.cpp shard_grm.cpp dist_solve.cpp session.cpp session_reml.cpp session_linear.cpp session_gwas.cpp session_pcs.cpp session_pairscan.cpp knobs.cpp hostpack.cpp; do
   o="$OUT/$f.o"
   objs+=("$o")
   HO=""

@@ -90,7 +90,7 @@ def main():
     torch.cuda.synchronize()
     G0 = st.G[: st.npad].clone()
     npad = st.npad
-    # the session's default chunk (csrc/session.cpp gwas_chunk): one 64-row strip per compute unit, balanced
+    # the session's default chunk (csrc/session_gwas.cpp gwas_chunk): one 64-row strip per compute unit, balanced
     ncu = torch.cuda.get_device_properties(st.dev).multi_processor_count
     strips = (p + 63) // 64
     cap = max(1, (768 << 20) // (npad * 8 * 64))
