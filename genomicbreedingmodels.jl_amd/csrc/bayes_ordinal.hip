@@ -152,6 +152,18 @@ __global__ void __launch_bounds__(256) ordinal_final_kernel(const double* __rest
   st->it += 1;
 }
 
+// gbm_debug_ordinal_math: gibbs_common.h's Φ (what 0), Φ⁻¹ (1) and TN (2; four inputs per item), one item each
+__host__ __device__ inline double ordinal_math(int what, const double* in, int64_t i) {
+  if (what == 0) return gibbs_phi(in[i]);
+  if (what == 1) return gibbs_ppnd16(in[i]);
+  return gibbs_truncnorm(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3]);
+}
+__global__ void __launch_bounds__(256) ordinal_math_kernel(int what, const double* __restrict__ in, int64_t m,
+                                                           double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < m) out[i] = ordinal_math(what, in, i);
+}
+
 // the classes of y (sorted distinct values), every individual's class and the start thresholds
 // t_k = Φ⁻¹(cum_k / n); host only
 struct OrdinalClasses {
@@ -288,5 +300,27 @@ extern "C" int gbm_bayes_fit_ordinal(int model, const double* X, int64_t n, int6
                            b_hat_out, y_pred_out, var_out, pip_out, thresholds_out, probs_out, ldprobs));
   *nclass_out = (int64_t)oc.values.size();
   std::copy(oc.values.begin(), oc.values.end(), classes_out);
+  return GBM_OK;
+}
+
+extern "C" int gbm_debug_ordinal_math(int what, const double* in, int64_t m, int device, double* host_out,
+                                      double* dev_out) {
+  set_error("");
+  if (!in || !host_out || m < 1 || m > ((int64_t)1 << 20) || what < 0 || what > 2)
+    return fail(GBM_E_ARG, "gbm_debug_ordinal_math: in and host_out non-NULL, 1 <= m <= 2^20, what in 0, 1, 2");
+  for (int64_t i = 0; i < m; i++) host_out[i] = ordinal_math(what, in, i);
+  if (!dev_out) return GBM_OK;  // host only: no device work
+  std::vector<int> devs;
+  GBM_TRY(check_devices(&device, 1, devs));
+  const int dev = devs[0];
+  GBM_HIP_TRY(hipSetDevice(dev));
+  const int64_t nin = what == 2 ? 4 * m : m;
+  DevBuf din, dout;
+  GBM_TRY(ensure(din, dev, nin * 8));
+  GBM_TRY(ensure(dout, dev, m * 8));
+  GBM_HIP_TRY(hipMemcpy(din.p, in, (size_t)(nin * 8), hipMemcpyHostToDevice));
+  ordinal_math_kernel<<<(unsigned)((m + 255) / 256), 256>>>(what, (const double*)din.p, m, (double*)dout.p);
+  GBM_LAUNCH_CHECK();
+  GBM_HIP_TRY(hipMemcpy(dev_out, dout.p, (size_t)(m * 8), hipMemcpyDeviceToHost));
   return GBM_OK;
 }

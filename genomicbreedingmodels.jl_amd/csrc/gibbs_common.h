@@ -68,7 +68,9 @@ __host__ __device__ inline double gibbs_ppnd16(double p) {
          42.313330701600911252) * r + 1.0;
     return q * num / den;
   }
-  double r = sqrt(-log(q < 0.0 ? p : 1.0 - p));
+  const double tail = q < 0.0 ? p : 1.0 - p;
+  if (tail <= 0.0) return q < 0.0 ? -INFINITY : INFINITY;  // sqrt(−log 0) = ∞ would end as ∞/∞ below
+  double r = sqrt(-log(tail));
   double val;
   if (r <= 5.0) {
     r -= 1.6;
@@ -97,7 +99,9 @@ __host__ __device__ inline double gibbs_ppnd16(double p) {
 }
 // TN(m; a, b; u): the N(m, 1) variate truncated to [a, b] (a < b, at most one of them infinite) by inverse CDF
 // from one uniform u, worked in the tail below the mean (an interval above it is reflected), where Φ keeps
-// its relative precision.
+// its relative precision. The draw is always finite: pa + u·w can round to 0 (a half-open class 37.6 to 38.5
+// below its mean: w is subnormal, u small) or to 1 (a half-open interval around the mean, u → 1), where Φ⁻¹
+// is infinite; then, as when the interval has no mass in fp64, the draw is the finite end nearer the mean.
 __host__ __device__ inline double gibbs_truncnorm(double m, double a, double b, double u) {
   double al = a - m, be = b - m;
   const bool refl = al >= 0.0;
@@ -107,14 +111,13 @@ __host__ __device__ inline double gibbs_truncnorm(double m, double a, double b, 
     be = -t;
   }
   const double pa = gibbs_phi(al), w = gibbs_phi(be) - pa;
-  double x;
+  double x = INFINITY;
   if (w > 0.0) {
     x = gibbs_ppnd16(pa + u * w);
     x = x < al ? al : x;
     x = x > be ? be : x;
-  } else {
-    x = fabs(be) <= fabs(al) ? be : al;  // no mass in fp64: the end nearer the mean (finite)
   }
+  if (!(fabs(x) < INFINITY)) x = fabs(be) <= fabs(al) ? be : al;  // at most one end is infinite
   return refl ? m - x : m + x;
 }
 

@@ -48,7 +48,7 @@ EXPORTS = (
     "gbm_debug_chol_flow_order_check", "gbm_debug_chol_flow_order_size", "gbm_dev_grm_exact_status", "gbm_debug_set",
     "gbm_dev_whiten_rows", "gbm_session_gwas", "gbm_session_enet_path", "gbm_dev_standardize_grm_syrk",
     "gbm_dev_grm_symmetrize", "gbm_dev_rows_times_sym", "gbm_dev_rows_times_sym_workspace", "gbm_session_pcs",
-    "gbm_debug_sym_eig", "gbm_session_pair_scan", "gbm_bayes_fit_ordinal",
+    "gbm_debug_sym_eig", "gbm_session_pair_scan", "gbm_bayes_fit_ordinal", "gbm_debug_ordinal_math",
 )
 
 GBM_GRM_DEFAULT, GBM_GRM_FP64, GBM_GRM_EXACT, GBM_GRM_AUTO, GBM_GRM_DROPIN = -1, 0, 1, 2, 3
@@ -270,6 +270,8 @@ def _declare(lib):
     lib.gbm_debug_sym_eig.argtypes = [P, I32, P, P]
     lib.gbm_debug_set.restype = I32
     lib.gbm_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+    lib.gbm_debug_ordinal_math.restype = I32
+    lib.gbm_debug_ordinal_math.argtypes = [I32, P, I64, I32, P, P]
     return lib
 
 

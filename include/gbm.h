@@ -754,9 +754,11 @@ int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx,
  *   [t_{z_i}, t_{z_i+1}]. varE ≡ 1 is never drawn.
  * Truncated normal TN(m; a, b; u), by inverse CDF from one uniform u: α = a − m, β = b − m; if α >= 0
  *   reflect, (α, β) ← (−β, −α); pa = Φ(α), pb = Φ(β); x = Φ⁻¹(pa + u (pb − pa)) clamped to [α, β], or,
- *   when pb − pa is not > 0, the end of [α, β] nearer 0; the result is m − x after a reflection, else
- *   m + x. Φ(x) = erfc(−x/√2)/2 (0 at −∞, 1 at +∞); Φ⁻¹ is Wichura's AS241 PPND16 in fp64, the library's
- *   own routine (csrc/gibbs_common.h).
+ *   when pb − pa is not > 0 or that x is not finite (pa + u (pb − pa) rounded to 0 or to 1, where Φ⁻¹ is
+ *   −∞ or +∞, in an interval whose end on that side is infinite), the finite end of [α, β] nearer 0 (at
+ *   most one end is infinite); the result is m − x after a reflection, else m + x: always finite.
+ *   Φ(x) = erfc(−x/√2)/2 (0 at −∞, 1 at +∞); Φ⁻¹ is Wichura's AS241 PPND16 in fp64, the library's own
+ *   routine (csrc/gibbs_common.h), with Φ⁻¹(p <= 0) = −∞ and Φ⁻¹(p >= 1) = +∞.
  * Start: y*_i = TN(0; t_{z_i}, t_{z_i+1}; u01(seed, 2^64 − 1, i)); vy = var(y*) (ddof 1), μ = mean(y*),
  *   e = y* − μ; every other start value and prior quantity as gbm_bayes_fit's from this vy (S0e is
  *   unused), varE = 1.
@@ -832,6 +834,11 @@ int gbm_debug_set(const char* name, const char* value);
  * method gbm_session_pcs runs on its 32 x 32 projected matrix (host only, no device work): w (m) descending,
  * V (m x m): V[i·m + r] = component r of the unit eigenvector of w[i]. */
 int gbm_debug_sym_eig(const double* A, int m, double* w, double* V);
+/* The ordinal sampler's own Φ, Φ⁻¹ and TN (gbm_bayes_fit_ordinal; csrc/gibbs_common.h) on m items: what 0:
+ * Φ(in[i]); 1: Φ⁻¹(in[i]); 2: TN(m; a, b; u) with in[4i … 4i+3] = (m, a, b, u). host_out (m) is the host
+ * compilation's result; dev_out (m; may be NULL: then host only, no device work) the device's, one kernel with
+ * one thread per item. GBM_E_ARG for NULL in or host_out, m < 1, m > 2^20 or another what. No fit calls it. */
+int gbm_debug_ordinal_math(int what, const double* in, int64_t m, int device, double* host_out, double* dev_out);
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 // beside asan_driver.cpp: the host code of gbm_bayes_fit_ordinal in front of its first device call. The class
 // scan (sort, distinct values, class of every individual, start thresholds through AS241) runs on real arrays
 // for K = 1, 2, 3, 32 and 33 and capacities below and at K; with no device the calls that pass every argument
-// check end in GBM_E_NODEV, the others in GBM_E_ARG with the entry's name in the message. Test infrastructure only.
+// check end in GBM_E_NODEV, the others in GBM_E_ARG with the entry's name in the message. Then the host half of
+// gbm_debug_ordinal_math (Φ, Φ⁻¹, TN of csrc/gibbs_common.h) and its argument checks. Test infrastructure only.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -49,6 +50,23 @@ int main() {
   for (int k : {2, 3, 32}) {
     const int rc = fit(70, 20, k, k);
     CHECK(rc == GBM_E_NODEV || rc == GBM_OK);
+  }
+  // gbm_debug_ordinal_math, host only (dev_out = NULL): buffers of exactly m (4 m for TN) values, the ends of
+  // Φ⁻¹, a draw where u Φ(β) rounds to 0 and one where pa + u (1 − pa) rounds to 1: both finite, the interval's end
+  {
+    const std::vector<double> p = {0.0, 0.5, 1.0}, tn = {38.0, -inf, 0.0, 0x1p-54, 1.0, 0.0, inf, 1.0 - 0x1p-53};
+    std::vector<double> out(3), draws(2);
+    CHECK(gbm_debug_ordinal_math(1, p.data(), 3, 0, out.data(), nullptr) == GBM_OK);
+    CHECK(out[0] == -inf && out[1] == 0.0 && out[2] == inf);
+    CHECK(gbm_debug_ordinal_math(0, p.data(), 3, 0, out.data(), nullptr) == GBM_OK && out[0] == 0.5);
+    CHECK(gbm_debug_ordinal_math(2, tn.data(), 2, 0, draws.data(), nullptr) == GBM_OK);
+    CHECK(draws[0] == 0.0 && draws[1] == 0.0);
+    CHECK(gbm_debug_ordinal_math(3, p.data(), 3, 0, out.data(), nullptr) == GBM_E_ARG &&
+          std::strstr(gbm_last_error(), "gbm_debug_ordinal_math"));
+    CHECK(gbm_debug_ordinal_math(1, nullptr, 3, 0, out.data(), nullptr) == GBM_E_ARG);
+    CHECK(gbm_debug_ordinal_math(1, p.data(), 3, 0, nullptr, nullptr) == GBM_E_ARG);
+    CHECK(gbm_debug_ordinal_math(1, p.data(), 0, 0, out.data(), nullptr) == GBM_E_ARG);
+    CHECK(gbm_debug_ordinal_math(1, p.data(), ((int64_t)1 << 20) + 1, 0, out.data(), nullptr) == GBM_E_ARG);
   }
   if (failures) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);

@@ -65,9 +65,10 @@ def truncnorm(m, a, b, u):
         al, be = -be, -al
     pa = phi(al)
     w = phi(be) - pa
+    x = math.inf
     if w > 0.0:
         x = min(max(ppnd16(pa + u * w), al), be)
-    else:
+    if not math.isfinite(x):  # no mass, or pa + u w rounded to 0 or 1: the finite end nearer the mean
         x = be if abs(be) <= abs(al) else al
     return m - x if refl else m + x
 

@@ -53,7 +53,8 @@ def test_as241_agrees_with_scipy():
 
 def test_library_as241_has_the_restatement_coefficients():
     """csrc/gibbs_common.h's gibbs_ppnd16 and the restatement hold the same constants in the same order
-    (the device routine's values are compared on the GPU only where the chains happen to go)."""
+    (the routines' own values, host and device, are held to an mpmath reference through gbm_debug_ordinal_math:
+    tests/test_ordinal_cases.py, tests/test_gpu_ordinal_edges.py)."""
     import inspect
     import os
     import re
