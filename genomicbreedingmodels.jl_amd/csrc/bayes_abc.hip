@@ -11,15 +11,20 @@
 // column k of the block's Gram matrix. bayes_prep_kernel forms, for every marker and in parallel,
 // everything of its step that does not depend on the chain (the normal, logit(u), 1/C, the square
 // roots), so that a chain step is FMAs, one compare, selects and one lane broadcast.
+//
+// gbm_bayes_fit_multi runs up to 32 such chains (a model, phenotype column, priors and seed each) over one X
+// in one pass: the same kernels with a chain index, each chain's bits those of gbm_bayes_fit.
 #include "gibbs_common.h"
 
 namespace gbm {
 namespace {
 
-// the intercept step of brr_mu_kernel on the stream A = 8 it
-__global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, int64_t n,
+// the intercept step of brr_mu_kernel on the stream A = 8 it; workgroup c is chain c (e at c·lde, state c)
+__global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, int64_t lde, int64_t n,
                                                         BayesState* __restrict__ st) {
   __shared__ double red[16];
+  e += (int64_t)blockIdx.x * lde;
+  st += blockIdx.x;
   const double mu_old = st->mu;
   double s = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 1024) s += e[i] + mu_old;
@@ -35,13 +40,20 @@ __global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, 
 //   0: x2 eff   1: eff = d b (old)   2: a = 1/(varE C)   3: c = sqrt(1/C) ξ   4: sqrt(varB) ξ
 //   5: b/(2 varE)   6: −b x2   7: log(π/(1−π)) − logit(u)
 // so that with r = x_jᵀe + x2 eff:  logOdds − logit(u) = pk5 (2 r + pk6) + pk7,  b_in = a r + c.
-// BayesA: pk5 = pk6 = 0, pk7 = 1 (always included).
+// BayesA: pk5 = pk6 = 0, pk7 = 1 (always included). blockIdx.y is the chain (x2 is common; b and d at
+// c·2p, varB at c·p, pk at c·8·ppad, state c).
 __global__ void __launch_bounds__(256) bayes_prep_kernel(int64_t p, int64_t ppad, const double* __restrict__ x2,
                                                          const double* __restrict__ b, const double* __restrict__ d,
                                                          const double* __restrict__ varB,
                                                          const BayesState* __restrict__ st, double* __restrict__ pk) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= ppad) return;
+  const int64_t ch = blockIdx.y;
+  b += ch * 2 * p;
+  d += ch * 2 * p;
+  varB += ch * p;
+  st += ch;
+  pk += ch * 8 * ppad;
   double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (j < p) {
     const int64_t par = st->it & 1;
@@ -77,10 +89,20 @@ __global__ void __launch_bounds__(256) bayes_prep_kernel(int64_t p, int64_t ppad
 // formed again from it after the chain: same operands, same bits as the value it broadcast). Wave 0
 // of every workgroup runs the chain from identical inputs; then e += X_B δ and the next block's
 // partials as in brr_step_kernel. Workgroup 0 stores b, d and the running means of d b and d.
-template <typename T>
+//
+// Several chains over one X (gbm_bayes_fit_multi): the grid is (chunks, ⌈nch/CH⌉) and workgroup row y
+// holds the chains CH·y … CH·y + CH − 1 (those below nch). CH = 1 is the kernel above, one chain per
+// row. With CH = 4 wave w runs the 64 steps of the row's chain w, where wave 0 alone runs them for
+// CH = 1; the block's rows in LDS, the thread's 64 genotypes and W are read once for the four chains,
+// and d⁰, e += X_B δ and the next block's partials are formed per chain by all four waves with the
+// operations and the order of CH = 1, so a chain's bits do not depend on CH, on its slot or on its
+// neighbours. Chain c's buffers: e at c·ldx, b and d at c·2p, the running means at c·p, pk at
+// c·8·64·nblk, its ping-pong partials at c·2·64·chunks, state c. ROWS = false (CH = 1, one chain: the
+// launch of gbm_bayes_fit) compiles the chain index out.
+template <typename T, int CH, bool ROWS>
 __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ Xt, int64_t ldx, int64_t n,
                                                           int64_t p, double xs, const double* __restrict__ W,
-                                                          int64_t blk, int64_t nblk,
+                                                          int64_t blk, int64_t nblk, int nch,
                                                           const double* __restrict__ partial_in,
                                                           double* __restrict__ partial_out,
                                                           const double* __restrict__ pk, double* __restrict__ b,
@@ -89,10 +111,17 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
                                                           const BayesState* __restrict__ st) {
   constexpr int RP = IW + 2;  // doubles (row pitch 2064 B, as brr_step_kernel)
   __shared__ __attribute__((aligned(16))) double Xn[BB * RP];
-  __shared__ double delta[BB];
-  __shared__ double es[IW];
-  __shared__ double part4[4][BB];
+  __shared__ double delta[CH][BB];
+  __shared__ double es[CH][IW];
+  __shared__ double part4[CH][4][BB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  static_assert(ROWS || CH == 1, "a launch without chain rows runs one chain");
+  const int ch0 = ROWS ? (int)blockIdx.y * CH : 0;                 // the row's first chain
+  const int nc = ROWS ? (nch - ch0 < CH ? nch - ch0 : CH) : 1;     // its chains (>= 1)
+  const int mine = CH == 1 ? 0 : wave;                     // the slot whose chain this wave runs
+  const bool runner = CH == 1 ? tid < 64 : wave < nc;      // this wave runs a chain
+  const int64_t ch = ch0 + (runner ? mine : 0);            // that chain
+  const int64_t pstride = 2 * (int64_t)gridDim.x * BB;     // a chain's ping-pong partials
   const int64_t j0 = blk * BB;
   const int nb = (int)((p - j0) < BB ? (p - j0) : BB);
   const int C = (int)gridDim.x;
@@ -124,13 +153,15 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
   double xv[BB];
 #pragma unroll
   for (int s2 = 0; s2 < BB; s2++) xv[s2] = gval<T>(Xt[(j0 + (s2 < nb ? s2 : 0)) * ldx + i], xs);
-  const double e_old = e[i];
-  // (3) wave 0's operands: column `lane` of W (= its row: W is symmetric) and the step constants
+  double e_old[CH];
+#pragma unroll
+  for (int c = 0; c < CH; c++) e_old[c] = c < nc ? e[(ch0 + c) * ldx + i] : 0.0;
+  // (3) a running wave's operands: column `lane` of W (= its row: W is symmetric) and the step constants
   double w[BB];
   double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const bool on = lane < nb;
   const int64_t j = j0 + lane;
-  if (tid < 64) {
+  if (runner) {
     const double* wr = W + (blk * BB + lane) * BB;
 #pragma unroll
     for (int s = 0; s < BB; s += 2) {
@@ -138,7 +169,7 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
       w[s] = v.x;
       w[s + 1] = v.y;
     }
-    const double2* pq = reinterpret_cast<const double2*>(pk + 8 * j);  // padded to whole blocks
+    const double2* pq = reinterpret_cast<const double2*>(pk + (ch * nblk * BB + j) * 8);  // padded to whole blocks
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const double2 v = pq[u];
@@ -146,22 +177,25 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
       q[2 * u + 1] = v.y;
     }
   }
-  const bool keeper = blockIdx.x == 0 && tid < 64 && on;
-  const double bb_old = keeper ? bbar[j] : 0.0, db_old = keeper ? dbar[j] : 0.0;
-  {
+  const bool keeper = blockIdx.x == 0 && runner && on;
+  const double bb_old = keeper ? bbar[ch * p + j] : 0.0, db_old = keeper ? dbar[ch * p + j] : 0.0;
+#pragma unroll
+  for (int c = 0; c < CH; c++) {
+    if (c >= nc) break;
+    const double* pin = partial_in + (ch0 + c) * pstride;
     double a = 0.0;
     for (int c0 = wave; c0 < C; c0 += 64) {
       double v[16];
 #pragma unroll
-      for (int m = 0; m < 16; m++) v[m] = partial_in[min(c0 + 4 * m, C - 1) * BB + lane];  // unconditional loads
+      for (int m = 0; m < 16; m++) v[m] = pin[min(c0 + 4 * m, C - 1) * BB + lane];  // unconditional loads
 #pragma unroll
       for (int m = 0; m < 16; m++) a += c0 + 4 * m < C ? v[m] : 0.0;
     }
-    part4[wave][lane] = a;
+    part4[c][wave][lane] = a;
   }
   __syncthreads();
-  if (tid < 64) {
-    const double d0 = ((part4[0][lane] + part4[1][lane]) + part4[2][lane]) + part4[3][lane];
+  if (runner) {
+    const double d0 = ((part4[mine][0][lane] + part4[mine][1][lane]) + part4[mine][2][lane]) + part4[mine][3][lane];
 #pragma unroll
     for (int s = 0; s < BB; s++) w[s] = lane > s ? w[s] : 0.0;
     const double eff = q[1], qa = q[2], qc = q[3], bout = q[4], qbh = q[5], qm = q[6], qthr = q[7];
@@ -176,72 +210,96 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
     const double lo = fma(qbh, fma(2.0, r, qm), qthr);
     const double bin = fma(r, qa, qc);
     const bool inc = lo > 0.0;
-    delta[lane] = inc ? eff - bin : eff;
+    delta[mine][lane] = inc ? eff - bin : eff;
     if (keeper) {
+      const BayesState* sc = st + ch;
       const double bfin = inc ? bin : bout, dfin = inc ? 1.0 : 0.0;
-      const int64_t o = ((st->it & 1) ^ 1) * p + j;
+      const int64_t o = ch * 2 * p + ((sc->it & 1) ^ 1) * p + j;
       b[o] = bfin;
       d[o] = dfin;
-      if (brr_accumulate(st)) {
-        const double k = (double)(st->nsum + 1);
-        bbar[j] = bb_old * ((k - 1.0) / k) + (inc ? bfin : 0.0) / k;
-        dbar[j] = db_old * ((k - 1.0) / k) + dfin / k;
+      if (brr_accumulate(sc)) {
+        const double k = (double)(sc->nsum + 1);
+        bbar[ch * p + j] = bb_old * ((k - 1.0) / k) + (inc ? bfin : 0.0) / k;
+        dbar[ch * p + j] = db_old * ((k - 1.0) / k) + dfin / k;
       }
     }
   }
   __syncthreads();
-  double ei = 0.0;
-  if (i < n) {
-    double acc0 = 0.0, acc1 = 0.0;
+  double ei[CH];
 #pragma unroll
-    for (int s2 = 0; s2 < BB; s2 += 2) {
-      acc0 = fma(delta[s2], xv[s2], acc0);
-      acc1 = fma(delta[s2 + 1], xv[s2 + 1], acc1);
+  for (int c = 0; c < CH; c++) {
+    ei[c] = 0.0;
+    if (c < nc && i < n) {
+      double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+      for (int s2 = 0; s2 < BB; s2 += 2) {
+        acc0 = fma(delta[c][s2], xv[s2], acc0);
+        acc1 = fma(delta[c][s2 + 1], xv[s2 + 1], acc1);
+      }
+      ei[c] = e_old[c] + (acc0 + acc1);
+      e[(ch0 + c) * ldx + i] = ei[c];
     }
-    ei = e_old + (acc0 + acc1);
-    e[i] = ei;
   }
   if (more) {
-    es[tid] = ei;
-    __syncthreads();  // also completes the global_load_lds of Xn
-    double s0 = 0.0, s1 = 0.0;
-    if (lane < nb1) {
-      const double* er = es + wave * 64;
-      if constexpr (sizeof(T) == 8) {
-        const double* xr = Xn + lane * RP + wave * 64;
 #pragma unroll
-        for (int u = 0; u < 64; u += 2) {
-          const double2 xv2 = *reinterpret_cast<const double2*>(xr + u);
-          s0 = fma(xv2.x, er[u], s0);
-          s1 = fma(xv2.y, er[u + 1], s1);
-        }
-      } else {
+    for (int c = 0; c < CH; c++)
+      if (c < nc) es[c][tid] = ei[c];
+    __syncthreads();  // also completes the global_load_lds of Xn
+    // byte storage: this lane's row, the wave's quarter (one read for the row's chains)
+    [[maybe_unused]] uint4 v[4] = {};
+    if constexpr (sizeof(T) != 8) {
+      if (lane < nb1) {
         const uint8_t* xr = Xb + lane * IW;
-        uint4 v[4];
 #pragma unroll
         for (int t = 0; t < 4; t++) v[t] = *reinterpret_cast<const uint4*>(xr + (((4 * wave + t) ^ (lane & 15)) * 16));
-        brr_dot64_u8(v, er, s0, s1);
-        s0 *= xs;
-        s1 *= xs;
       }
     }
-    part4[wave][lane] = s0 + s1;
+#pragma unroll
+    for (int c = 0; c < CH; c++) {
+      if (c >= nc) break;
+      double s0 = 0.0, s1 = 0.0;
+      if (lane < nb1) {
+        const double* er = es[c] + wave * 64;
+        if constexpr (sizeof(T) == 8) {
+          const double* xr = Xn + lane * RP + wave * 64;
+#pragma unroll
+          for (int u = 0; u < 64; u += 2) {
+            const double2 xv2 = *reinterpret_cast<const double2*>(xr + u);
+            s0 = fma(xv2.x, er[u], s0);
+            s1 = fma(xv2.y, er[u + 1], s1);
+          }
+        } else {
+          brr_dot64_u8(v, er, s0, s1);
+          s0 *= xs;
+          s1 *= xs;
+        }
+      }
+      part4[c][wave][lane] = s0 + s1;
+    }
     __syncthreads();
-    if (tid < 64)
-      partial_out[blockIdx.x * BB + lane] = ((part4[0][lane] + part4[1][lane]) + part4[2][lane]) + part4[3][lane];
+    if (runner)
+      partial_out[ch * pstride + blockIdx.x * BB + lane] =
+          ((part4[mine][0][lane] + part4[mine][1][lane]) + part4[mine][2][lane]) + part4[mine][3][lane];
   }
 }
 
 // Per-marker variances (BayesA, BayesB: varB_j = (S + b_j²)/χ²(df0 + 1) on the stream PM(it, j))
 // and, per workgroup, the partial sums vpart[5 blk ..] = Σ 1/varB_j, Σ d_j, Σ b_j², Σ varB_j over
 // its 256 markers and Σ e_i² over its 256 individuals (no atomics: bayes_final_kernel adds the
-// workgroups' partials in index order).
+// workgroups' partials in index order). blockIdx.y is the chain (e at c·lde, vpart at c·5·gridDim.x).
 __global__ void __launch_bounds__(256) bayes_var_kernel(const double* __restrict__ b, const double* __restrict__ d,
                                                         double* __restrict__ varB, int64_t p,
-                                                        const double* __restrict__ e, int64_t n,
+                                                        const double* __restrict__ e, int64_t lde, int64_t n,
                                                         const BayesState* __restrict__ st,
                                                         double* __restrict__ vpart) {
   __shared__ double red[4];
+  const int64_t ch = blockIdx.y;
+  b += ch * 2 * p;
+  d += ch * 2 * p;
+  varB += ch * p;
+  e += ch * lde;
+  st += ch;
+  vpart += ch * 5 * (int64_t)gridDim.x;
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t par = (st->it & 1) ^ 1;  // this iteration's samples
   double v[5] = {0, 0, 0, 0, 0};
@@ -266,10 +324,12 @@ __global__ void __launch_bounds__(256) bayes_var_kernel(const double* __restrict
 }
 
 // The scalar draws of an iteration (one workgroup): S, BayesC's common varB, π, varE; the running
-// means of μ, varE, mean_j varB_j and π; next iteration.
+// means of μ, varE, mean_j varB_j and π; next iteration. Workgroup c is chain c.
 __global__ void __launch_bounds__(256) bayes_final_kernel(const double* __restrict__ vpart, int64_t nvb, int64_t p,
                                                           int64_t n, BayesState* __restrict__ st) {
   __shared__ double red[4];
+  vpart += (int64_t)blockIdx.x * 5 * nvb;
+  st += blockIdx.x;
   double sum[5];
 #pragma unroll
   for (int u = 0; u < 5; u++) {
@@ -329,21 +389,32 @@ int bayes_check_args(const char* entry, int model, const double* X, const double
   return GBM_OK;
 }
 
-int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64_t n, int64_t p, int64_t ldx,
-                const double* y, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
-                uint64_t seed, GibbsData& g, BayesState& st0) {
+int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, int64_t nchains, GibbsData& g) {
   const int dev = cx.dev;
-  hipStream_t s = cx.stream.s;
-  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB;
-  GBM_TRY(ensure(cx.dind, dev, 2 * p * 8));  // two copies (iteration parity), as b
-  GBM_TRY(ensure(cx.dbar, dev, p * 8));
-  GBM_TRY(ensure(cx.varBj, dev, p * 8));
-  GBM_TRY(ensure(cx.pk, dev, ppad * 8 * 8));
-  GBM_TRY(ensure(cx.vpart, dev, bayes_var_blocks(n, p) * 5 * 8));
+  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB, T = nchains;
+  const int64_t npad = round_up(n, IW), C = (n + IW - 1) / IW;
+  GBM_TRY(ensure(cx.dind, dev, T * 2 * p * 8));  // two copies (iteration parity), as b
+  GBM_TRY(ensure(cx.dbar, dev, T * p * 8));
+  GBM_TRY(ensure(cx.varBj, dev, T * p * 8));
+  GBM_TRY(ensure(cx.pk, dev, T * ppad * 8 * 8));
+  GBM_TRY(ensure(cx.vpart, dev, T * bayes_var_blocks(n, p) * 5 * 8));
+  if (T > 1) {  // the per-chain copies of what gibbs_upload sizes for one chain
+    GBM_TRY(ensure(cx.e, dev, T * npad * 8));
+    GBM_TRY(ensure(cx.b, dev, T * 2 * p * 8));
+    GBM_TRY(ensure(cx.bbar, dev, T * p * 8));
+    GBM_TRY(ensure(cx.r, dev, std::max<int64_t>(T * 2 * C * BB, 2 * C * BK2) * 8));
+  }
   GBM_TRY(gibbs_upload(cx, X, n, p, ldx, g));
+  GBM_TRY(gibbs_gram(cx, n, p, g.npad, nblk, 1));
+  GBM_HIP_TRY(hipStreamSynchronize(cx.stream.s));
+  return GBM_OK;
+}
+
+int bayes_start(const char* entry, BrrCtx& cx, int64_t chain, int model, int64_t n, int64_t p, const double* y,
+                int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts, uint64_t seed,
+                const GibbsData& g, BayesState& st0) {
+  hipStream_t s = cx.stream.s;
   const int64_t npad = g.npad;
-  GBM_TRY(gibbs_gram(cx, n, p, npad, nblk, 1));
-  GBM_HIP_TRY(hipStreamSynchronize(s));
   GibbsPrior pr;
   GBM_TRY(gibbs_prior(entry, y, n, p, g, pr));
   const double shape0 = 1.1;
@@ -365,48 +436,72 @@ int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64
   st0.thin = thin;
   st0.seed = seed;
   st0.model = model;
+  double* e = (double*)cx.e.p + chain * npad;
+  double* b = (double*)cx.b.p + chain * 2 * p;
+  double* d = (double*)cx.dind.p + chain * 2 * p;
   std::vector<double> init(2 * p, 1.0);  // d = 1; then varB_j = S0/(df0 + 2)
-  GBM_HIP_TRY(hipMemcpyAsync(cx.e.p, pr.e0.data(), npad * 8, hipMemcpyHostToDevice, s));
-  GBM_HIP_TRY(hipMemcpyAsync(cx.dind.p, init.data(), 2 * p * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(e, pr.e0.data(), npad * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(d, init.data(), 2 * p * 8, hipMemcpyHostToDevice, s));
   GBM_HIP_TRY(hipStreamSynchronize(s));
   std::fill(init.begin(), init.begin() + p, st0.varBc);
-  GBM_HIP_TRY(hipMemcpyAsync(cx.varBj.p, init.data(), p * 8, hipMemcpyHostToDevice, s));
-  GBM_HIP_TRY(hipMemsetAsync(cx.b.p, 0, 2 * p * 8, s));
-  GBM_HIP_TRY(hipMemsetAsync(cx.bbar.p, 0, p * 8, s));
-  GBM_HIP_TRY(hipMemsetAsync(cx.dbar.p, 0, p * 8, s));
+  GBM_HIP_TRY(hipMemcpyAsync((double*)cx.varBj.p + chain * p, init.data(), p * 8, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemsetAsync(b, 0, 2 * p * 8, s));
+  GBM_HIP_TRY(hipMemsetAsync((double*)cx.bbar.p + chain * p, 0, p * 8, s));
+  GBM_HIP_TRY(hipMemsetAsync((double*)cx.dbar.p + chain * p, 0, p * 8, s));
   GBM_HIP_TRY(hipStreamSynchronize(s));  // init leaves scope
   return GBM_OK;
 }
 
-void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* stp) {
+int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64_t n, int64_t p, int64_t ldx,
+                const double* y, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
+                uint64_t seed, GibbsData& g, BayesState& st0) {
+  GBM_TRY(bayes_setup_shared(cx, X, n, p, ldx, 1, g));
+  return bayes_start(entry, cx, 0, model, n, p, y, n_burnin, thin, r2, df0, prob_in, counts, seed, g, st0);
+}
+
+namespace {
+template <typename T, int CH, bool ROWS>
+void launch_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, int64_t k, int64_t nblk, int64_t nchains,
+                  BayesState* stp) {
+  const int64_t C = g.C64;
+  const T* X = sizeof(T) == 8 ? (const T*)cx.Xt.p : (const T*)cx.D.p;
+  const double* pin = (const double*)cx.r.p + (k & 1) * C * BB;
+  double* pout = (double*)cx.r.p + ((k + 1) & 1) * C * BB;
+  bayes_chain_kernel<T, CH, ROWS><<<dim3((unsigned)C, (unsigned)((nchains + CH - 1) / CH)), 256, 0, cx.stream.s>>>(
+      X, g.npad, n, p, sizeof(T) == 8 ? 1.0 : g.xs, (const double*)cx.W.p, k, nblk, (int)nchains, pin, pout,
+      (const double*)cx.pk.p, (double*)cx.b.p, (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
+      (double*)cx.e.p, stp);
+}
+}  // namespace
+
+void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* stp, int64_t nchains,
+                         int per_wg) {
   hipStream_t s = cx.stream.s;
-  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB, npad = g.npad;
-  const double xs = g.xs;
-  const unsigned C = (unsigned)g.C64;
-  bayes_prep_kernel<<<(unsigned)(ppad / 256 + 1), 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
-                                                               (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
-                                                               (double*)cx.pk.p);
-  bayes_mu_kernel<<<1, 1024, 0, s>>>((double*)cx.e.p, n, stp);
-  gibbs_dots0(cx, n, p, g, xs > 0.0);
+  const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB;
+  const bool bytes = g.xs > 0.0;
+  bayes_prep_kernel<<<dim3((unsigned)(ppad / 256 + 1), (unsigned)nchains), 256, 0, s>>>(
+      p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p, (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
+      (double*)cx.pk.p);
+  bayes_mu_kernel<<<(unsigned)nchains, 1024, 0, s>>>((double*)cx.e.p, g.npad, n, stp);
+  gibbs_dots0(cx, n, p, g, bytes, nchains);
   for (int64_t k = 0; k < nblk; k++) {
-    double* pin = (double*)cx.r.p + (k & 1) * (int64_t)C * BB;
-    double* pout = (double*)cx.r.p + ((k + 1) & 1) * (int64_t)C * BB;
-    if (xs > 0.0)
-      bayes_chain_kernel<uint8_t><<<C, 256, 0, s>>>((const uint8_t*)cx.D.p, npad, n, p, xs, (const double*)cx.W.p, k,
-                                                    nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
-                                                    (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
-                                                    (double*)cx.e.p, stp);
-    else
-      bayes_chain_kernel<double><<<C, 256, 0, s>>>((const double*)cx.Xt.p, npad, n, p, 1.0, (const double*)cx.W.p, k,
-                                                   nblk, pin, pout, (const double*)cx.pk.p, (double*)cx.b.p,
-                                                   (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
-                                                   (double*)cx.e.p, stp);
+    if (per_wg == 4) {
+      if (bytes) launch_chain<uint8_t, 4, true>(cx, n, p, g, k, nblk, nchains, stp);
+      else launch_chain<double, 4, true>(cx, n, p, g, k, nblk, nchains, stp);
+    } else if (nchains > 1) {
+      if (bytes) launch_chain<uint8_t, 1, true>(cx, n, p, g, k, nblk, nchains, stp);
+      else launch_chain<double, 1, true>(cx, n, p, g, k, nblk, nchains, stp);
+    } else {
+      if (bytes) launch_chain<uint8_t, 1, false>(cx, n, p, g, k, nblk, 1, stp);
+      else launch_chain<double, 1, false>(cx, n, p, g, k, nblk, 1, stp);
+    }
   }
 }
 
-void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* stp) {
-  bayes_var_kernel<<<(unsigned)bayes_var_blocks(n, p), 256, 0, cx.stream.s>>>(
-      (const double*)cx.b.p, (const double*)cx.dind.p, (double*)cx.varBj.p, p, (const double*)cx.e.p, n, stp,
+void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* stp, int64_t nchains) {
+  const int64_t npad = round_up(n, IW);
+  bayes_var_kernel<<<dim3((unsigned)bayes_var_blocks(n, p), (unsigned)nchains), 256, 0, cx.stream.s>>>(
+      (const double*)cx.b.p, (const double*)cx.dind.p, (double*)cx.varBj.p, p, (const double*)cx.e.p, npad, n, stp,
       (double*)cx.vpart.p);
 }
 
@@ -473,3 +568,103 @@ extern "C" int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, i
                         y_pred_out, var_out, pip_out);
 }
 
+
+// gbm_bayes_fit_multi on a leased context: gbm_bayes_fit's setup once (genotypes, column statistics, byte
+// quantisation, Gram blocks), a start state per chain, then the iteration of all chains (the kernels of
+// gbm_bayes_fit with a chain index) captured as the context's multi graph and replayed; outputs per chain.
+static std::atomic<int64_t> g_multi_calls{0}, g_multi_chains{0};
+
+static int bayes_fit_multi_impl(int64_t T, const int* models, const double* X, int64_t n, int64_t p, int64_t ldx,
+                                const double* Y, int64_t ldy, int64_t n_iter, int64_t n_burnin, int64_t thin,
+                                const double* r2, const double* df0, const double* prob_in, const double* counts,
+                                const uint64_t* seeds, int dev, double* b_hat_out, int64_t ldb, double* y_pred_out,
+                                int64_t ldp, double* var_out, double* pip_out, int64_t ldpip) {
+  BrrLease lease;
+  GBM_TRY(CtxPool<BrrCtx>::instance().acquire(dev, lease.c));
+  BrrCtx& cx = *lease.c;
+  GBM_HIP_TRY(hipSetDevice(dev));
+  hipStream_t s = cx.stream.s;
+  GBM_TRY(ensure(cx.bst, dev, T * (int64_t)sizeof(BayesState)));
+  GibbsData g;
+  GBM_TRY(bayes_setup_shared(cx, X, n, p, ldx, T, g));
+  std::vector<BayesState> st0((size_t)T);
+  for (int64_t c = 0; c < T; c++) {
+    const std::string who = "gbm_bayes_fit_multi: chain " + std::to_string(c);
+    GBM_TRY(bayes_start(who.c_str(), cx, c, models[c], n, p, Y + c * ldy, n_burnin, thin, r2[c], df0[c], prob_in[c],
+                        counts[c], seeds[c], g, st0[(size_t)c]));
+  }
+  const int64_t npad = g.npad, nvb = bayes_var_blocks(n, p);
+  GBM_HIP_TRY(hipMemcpyAsync(cx.bst.p, st0.data(), (size_t)T * sizeof(BayesState), hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));
+  auto* stp = (BayesState*)cx.bst.p;
+  // Chains per workgroup row of the chain launch (the results have the same bits): one (the one-chain kernel on
+  // nchains rows) or four (a chain per wave). A workgroup holds a CU (LDS), so a launch runs in
+  // ⌈workgroups / CUs⌉ rounds; a round of four-chain workgroups takes twice a round of one-chain workgroups (each
+  // wave sums, updates and forms partials for four chains) and there are a quarter of the workgroups. The mapping
+  // with the shorter launch by that count is taken, one chain per row at a tie (measured at C4: DESIGN.md
+  // §4.6.3). GBM_BAYES_MULTI_WG = 1 or 4 forces the mapping (read per call).
+  int cus = 0;
+  GBM_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  cus = std::max(cus, 1);
+  const int64_t rounds1 = (g.C64 * T + cus - 1) / cus, rounds4 = (g.C64 * ((T + 3) / 4) + cus - 1) / cus;
+  const int64_t forced = knob_i64("GBM_BAYES_MULTI_WG", 0);
+  const int per_wg = forced == 1 ? 1 : forced == 4 ? 4 : (rounds1 <= 2 * rounds4 ? 1 : 4);
+  auto enqueue_iteration = [&]() -> int {
+    bayes_enqueue_chain(cx, n, p, g, stp, T, per_wg);
+    bayes_enqueue_var(cx, n, p, stp, T);
+    bayes_final_kernel<<<(unsigned)T, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp);
+    return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, "gbm_bayes_fit_multi: launch failed");
+  };
+  cx.multi_graph.ensure({T, per_wg, n, p, npad, (int64_t)(g.xs * 64.0), key_of(cx.Xt), key_of(cx.D), key_of(cx.W),
+                         key_of(cx.r), key_of(cx.e), key_of(cx.b), key_of(cx.dind), key_of(cx.bbar), key_of(cx.dbar),
+                         key_of(cx.varBj), key_of(cx.pk), key_of(cx.vpart), key_of(cx.x2), key_of(cx.bst)},
+                        s, enqueue_iteration);
+  GBM_TRY(cx.multi_graph.run(n_iter, s, "gbm_bayes_fit_multi", enqueue_iteration));
+  for (int64_t c = 0; c < T; c++) {
+    BayesState fin{};
+    GBM_TRY(gibbs_outputs(cx, n, p, npad, cx.bst, &fin, sizeof(fin), &fin.mubar, b_hat_out + c * ldb,
+                          pip_out ? pip_out + c * ldpip : nullptr, y_pred_out ? y_pred_out + c * ldp : nullptr, c));
+    if (var_out) {
+      var_out[3 * c] = fin.varEbar;
+      var_out[3 * c + 1] = fin.varBbar;
+      var_out[3 * c + 2] = fin.pibar;
+    }
+  }
+  g_multi_calls.fetch_add(1, std::memory_order_relaxed);
+  g_multi_chains.fetch_add(T, std::memory_order_relaxed);
+  return GBM_OK;
+}
+
+extern "C" int gbm_bayes_fit_multi(int64_t nchains, const int* models, const double* X, int64_t n, int64_t p,
+                                   int64_t ldx, const double* Y, int64_t ldy, int64_t n_iter, int64_t n_burnin,
+                                   int64_t thin, const double* r2, const double* df0, const double* prob_in,
+                                   const double* counts, const uint64_t* seeds, int device, double* b_hat_out,
+                                   int64_t ldb, double* y_pred_out, int64_t ldp, double* var_out, double* pip_out,
+                                   int64_t ldpip) {
+  RoctxRange r_("gbm_bayes_fit_multi");
+  set_error("");
+  if (nchains < 1 || nchains > GBM_BAYES_MAX_CHAINS)
+    return fail(GBM_E_ARG, "gbm_bayes_fit_multi: 1 <= nchains <= " + std::to_string(GBM_BAYES_MAX_CHAINS));
+  if (!models || !X || !Y || !r2 || !df0 || !prob_in || !counts || !seeds || !b_hat_out)
+    return fail(GBM_E_ARG, "gbm_bayes_fit_multi: models, X, Y, r2, df0, prob_in, counts, seeds and b_hat_out are required");
+  if (ldy < n || ldb < p + 1 || (y_pred_out && ldp < n) || (pip_out && ldpip < p))
+    return fail(GBM_E_ARG, "gbm_bayes_fit_multi: bad pitch (ldy >= n, ldb >= p + 1, ldp >= n, ldpip >= p)");
+  int dev = 0;
+  for (int64_t c = 0; c < nchains; c++) {
+    const std::string who = "gbm_bayes_fit_multi: chain " + std::to_string(c);
+    GBM_TRY(bayes_check_args(who.c_str(), models[c], X, Y + c * ldy, b_hat_out, n, p, ldx, n_iter, n_burnin, thin, r2[c],
+                             df0[c], prob_in[c], counts[c]));
+    // the phenotype checks speak of "phenotype 1": put the chain in front
+    const int rc = check_y(Y + c * ldy, n, n, 1);
+    if (rc != GBM_OK) return fail(rc, who + ": " + last_error());
+  }
+  GBM_TRY(gibbs_check_run("gbm_bayes_fit_multi", Y, n, n_iter, n_burnin, thin, device, dev));
+  return bayes_fit_multi_impl(nchains, models, X, n, p, ldx, Y, ldy, n_iter, n_burnin, thin, r2, df0, prob_in, counts,
+                              seeds, dev, b_hat_out, ldb, y_pred_out, ldp, var_out, pip_out, ldpip);
+}
+
+extern "C" int gbm_debug_bayes_multi_stats(int64_t* calls, int64_t* chains) {
+  if (calls) *calls = g_multi_calls.load(std::memory_order_relaxed);
+  if (chains) *chains = g_multi_chains.load(std::memory_order_relaxed);
+  return GBM_OK;
+}

@@ -2,7 +2,8 @@
 //   gibbs_setup.hip  the kernels, pooled context and host steps both samplers use;
 //   brr.hip          Bayesian ridge regression: the per-launch kernels, gbm_brr_fit, the debug exports;
 //   brr_sweep.hip    its persistent super-block sweep, behind brr_sweep_plan / _setup / _enqueue;
-//   bayes_abc.hip    BayesA, BayesB, BayesC: gbm_bayes_fit, and the steps the ordinal fit replays;
+//   bayes_abc.hip    BayesA, BayesB, BayesC: gbm_bayes_fit, gbm_bayes_fit_multi (several chains over one X),
+//                    and the steps the ordinal fit replays;
 //   bayes_ordinal.hip  their ordinal (threshold-model) response: gbm_bayes_fit_ordinal.
 //
 // Random numbers: a counter-based hash of (seed, stream, counter) (no sampler state), Box-Muller
@@ -286,7 +287,7 @@ inline int64_t key_of(const DevBuf& b) { return (int64_t)(uintptr_t)b.p; }  // a
 // Pooled per-device sampler contexts (as fit_ctx.h pools the GBLUP fit contexts): a fit leases one,
 // its buffers only grow, so repeated fits of one shape allocate no device memory after the first
 // (cvmultithread! runs bayesian("BRR") once per fold). BRR and BayesA/B/C fits that alternate on
-// one context keep both captured graphs; the ordinal fits have a third.
+// one context keep both captured graphs; the ordinal fits have a third, the multi-chain fits a fourth.
 struct BrrCtx {
   int dev = 0;
   Stream stream;
@@ -296,12 +297,13 @@ struct BrrCtx {
   DevBuf trace;                            // GBM_BRR_TRACE timestamps of this context's last sweep
   DevBuf dind, dbar, varBj, pk, vpart, bst;  // gbm_bayes_fit: indicators, PIP, varB_j, step constants, partial sums, state
   DevBuf oys, oyh, ocls, opart, oprob, ost;  // gbm_bayes_fit_ordinal: y*, ŷ, classes, min/max partials, P(class), state
-  IterGraph brr_graph, bayes_graph, ordinal_graph;
+  IterGraph brr_graph, bayes_graph, ordinal_graph, multi_graph;  // multi_graph: gbm_bayes_fit_multi
   ~BrrCtx() {
     (void)hipSetDevice(dev);
     brr_graph.drop();
     bayes_graph.drop();
     ordinal_graph.drop();
+    multi_graph.drop();
   }
 };
 struct BrrLease {
@@ -329,8 +331,9 @@ struct GibbsData {
 int gibbs_upload(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, GibbsData& g);
 // W = the Gram blocks of brr_gram_kernel (nw = 1 or 3) for nblk launches; sizes W
 int gibbs_gram(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, int64_t nblk, int nw);
-// block 0's partial dots into r, from the fp64 rows or (bytes) from D as 64-marker blocks
-void gibbs_dots0(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, bool bytes);
+// block 0's partial dots into r, from the fp64 rows or (bytes) from D as 64-marker blocks; for each of
+// nchains chains (chain c: e at c·npad, its ping-pong partials at c·2·C64·BB)
+void gibbs_dots0(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, bool bytes, int64_t nchains = 1);
 // BGLR's prior moments: ȳ, var(y) with ddof 1, MSx = Σ_j var(x_j), and the start residual y − ȳ
 struct GibbsPrior {
   double ym = 0.0, vy = 0.0, msx = 0.0;
@@ -338,9 +341,10 @@ struct GibbsPrior {
 };
 int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const GibbsData& g, GibbsPrior& pr);
 // The tail of a fit: the final state (fin_bytes from `state` into fin) and the posterior means to
-// the host, b_hat_out[0] = *mubar (a field of fin), then the optional y_pred = μ̄ + X b̄.
+// the host, b_hat_out[0] = *mubar (a field of fin), then the optional y_pred = μ̄ + X b̄. `chain`: which
+// chain of a multi-chain fit (entry `chain` of the state array, the means at chain·p).
 int gibbs_outputs(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, const DevBuf& state, void* fin, size_t fin_bytes,
-                  const double* mubar, double* b_hat_out, double* pip_out, double* y_pred_out);
+                  const double* mubar, double* b_hat_out, double* pip_out, double* y_pred_out, int64_t chain = 0);
 
 // ---- what gbm_bayes_fit shares with gbm_bayes_fit_ordinal (bayes_abc.hip) -------------------------
 // gbm_bayes_fit's argument checks in front of gibbs_check_run (`entry` opens the error text)
@@ -352,11 +356,20 @@ int bayes_check_args(const char* entry, int model, const double* X, const double
 int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64_t n, int64_t p, int64_t ldx,
                 const double* y, int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
                 uint64_t seed, GibbsData& g, BayesState& st0);
-// steps 1 and 2 of an iteration on the state st: the step constants, μ, block 0's partial dots, one chain
-// launch per 64-marker block
-void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* st);
+// The two halves of bayes_setup, which gbm_bayes_fit_multi calls once and once per chain. Shared: the buffers
+// sized for nchains chains, the genotypes and the Gram blocks (stream synchronised). Per chain: y's prior
+// moments, the start state st0 and the start values of the chain's e, b, d, varB_j and running means
+// (chain c's arrays lie at c times the one-chain size in the context's buffers).
+int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, int64_t nchains, GibbsData& g);
+int bayes_start(const char* entry, BrrCtx& cx, int64_t chain, int model, int64_t n, int64_t p, const double* y,
+                int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts, uint64_t seed,
+                const GibbsData& g, BayesState& st0);
+// steps 1 and 2 of an iteration on the states st[0 .. nchains): the step constants, μ, block 0's partial dots,
+// one chain launch per 64-marker block with per_wg (1 or 4) chains in a workgroup row
+void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* st, int64_t nchains = 1,
+                         int per_wg = 1);
 // step 3's per-marker variances and the partial sums of the scalar draws (vpart)
-void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* st);
+void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* st, int64_t nchains = 1);
 inline int64_t bayes_var_blocks(int64_t n, int64_t p) { return (std::max(n, p) + 255) / 256; }
 
 // ---- the super-block sweep's host interface (brr_sweep.hip) -----------------------------------------

@@ -43,12 +43,15 @@ __global__ void __launch_bounds__(256) brr_gram_kernel(const double* __restrict_
   brr_gram_tile(Xt, ldx, p, n, r0, c0, W + (int64_t)blockIdx.x * BB * BB, BB);
 }
 
-// partials of block 0 at the start of an iteration (after the intercept update)
+// partials of block 0 at the start of an iteration (after the intercept update); blockIdx.y is the
+// chain of a multi-chain fit (e at c·lde, its partials at c·ldr)
 template <typename T>
 __global__ void __launch_bounds__(256) brr_dots0_kernel(const T* __restrict__ Xt, int64_t ldx, int64_t n,
                                                         int64_t p, double xs, const double* __restrict__ e,
-                                                        double* __restrict__ partial) {
+                                                        int64_t lde, double* __restrict__ partial, int64_t ldr) {
   __shared__ double es[IW];
+  e += (int64_t)blockIdx.y * lde;
+  partial += (int64_t)blockIdx.y * ldr;
   const int64_t i0 = (int64_t)blockIdx.x * IW;
   es[threadIdx.x] = i0 + threadIdx.x < n ? e[i0 + threadIdx.x] : 0.0;
   __syncthreads();
@@ -182,13 +185,15 @@ int gibbs_gram(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, int64_t nblk, int
   return GBM_OK;
 }
 
-void gibbs_dots0(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, bool bytes) {
+void gibbs_dots0(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, bool bytes, int64_t nchains) {
+  const dim3 grid((unsigned)g.C64, (unsigned)nchains);
+  const int64_t ldr = 2 * g.C64 * BB;  // a chain's ping-pong pair
   if (bytes)
-    brr_dots0_kernel<uint8_t><<<(unsigned)g.C64, 256, 0, cx.stream.s>>>((const uint8_t*)cx.D.p, g.npad, n, p, g.xs,
-                                                                        (const double*)cx.e.p, (double*)cx.r.p);
+    brr_dots0_kernel<uint8_t><<<grid, 256, 0, cx.stream.s>>>((const uint8_t*)cx.D.p, g.npad, n, p, g.xs,
+                                                             (const double*)cx.e.p, g.npad, (double*)cx.r.p, ldr);
   else
-    brr_dots0_kernel<double><<<(unsigned)g.C64, 256, 0, cx.stream.s>>>((const double*)cx.Xt.p, g.npad, n, p, 1.0,
-                                                                       (const double*)cx.e.p, (double*)cx.r.p);
+    brr_dots0_kernel<double><<<grid, 256, 0, cx.stream.s>>>((const double*)cx.Xt.p, g.npad, n, p, 1.0,
+                                                            (const double*)cx.e.p, g.npad, (double*)cx.r.p, ldr);
 }
 
 int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const GibbsData& g, GibbsPrior& pr) {
@@ -215,12 +220,13 @@ int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const 
 }
 
 int gibbs_outputs(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, const DevBuf& state, void* fin, size_t fin_bytes,
-                  const double* mubar, double* b_hat_out, double* pip_out, double* y_pred_out) {
+                  const double* mubar, double* b_hat_out, double* pip_out, double* y_pred_out, int64_t chain) {
   const int dev = cx.dev;
   hipStream_t s = cx.stream.s;
-  GBM_HIP_TRY(hipMemcpyAsync(fin, state.p, fin_bytes, hipMemcpyDeviceToHost, s));
-  GBM_HIP_TRY(hipMemcpyAsync(b_hat_out + 1, cx.bbar.p, p * 8, hipMemcpyDeviceToHost, s));
-  if (pip_out) GBM_HIP_TRY(hipMemcpyAsync(pip_out, cx.dbar.p, p * 8, hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipMemcpyAsync(fin, (const char*)state.p + chain * (int64_t)fin_bytes, fin_bytes, hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipMemcpyAsync(b_hat_out + 1, (const double*)cx.bbar.p + chain * p, p * 8, hipMemcpyDeviceToHost, s));
+  if (pip_out)
+    GBM_HIP_TRY(hipMemcpyAsync(pip_out, (const double*)cx.dbar.p + chain * p, p * 8, hipMemcpyDeviceToHost, s));
   GBM_HIP_TRY(hipStreamSynchronize(s));
   b_hat_out[0] = *mubar;
   if (!y_pred_out) return GBM_OK;

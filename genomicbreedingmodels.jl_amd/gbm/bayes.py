@@ -109,6 +109,54 @@ def bayes_arrays(model: str, X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500
     return b_hat, y_pred, var, pip
 
 
+MAX_CHAINS = 32  # include/gbm.h GBM_BAYES_MAX_CHAINS
+
+
+def bayes_multi_arrays(models, X: np.ndarray, Y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500, thin: int = 5,
+                       r2=0.5, df0=5.0, prob_in=0.5, counts=10.0, seeds=42, device: int = 0):
+    """T = len(models) independent BayesA / BayesB / BayesC chains over one X in one pass (``gbm_bayes_fit_multi``):
+    chain c has the model ``models[c]``, the phenotypes ``Y[:, c]`` and entry c of ``r2``, ``df0``, ``prob_in``,
+    ``counts`` and ``seeds`` (a scalar serves every chain). Returns (b_hat (p+1, T), y_pred (n, T), var (3, T),
+    pip (p, T)); column c has the bits of ``bayes_arrays(models[c], X, Y[:, c], ...)`` with the chain's arguments."""
+    models = list(models)
+    for m in models:
+        if m not in BAYES_MODELS:
+            raise ArgumentError(f"model `{m}` is not one of {tuple(BAYES_MODELS)}")
+    T = len(models)
+    if not 1 <= T <= MAX_CHAINS:
+        raise ArgumentError(f"bayes_multi_arrays runs 1 to {MAX_CHAINS} chains per call, got {T}")
+    X = np.asfortranarray(np.asarray(X, dtype=np.float64))
+    Y = np.asarray(Y, dtype=np.float64)
+    n, p = X.shape
+    if Y.ndim != 2 or Y.shape != (n, T):
+        raise ArgumentError(f"Y must have one column of {n} phenotypes per chain, ({n}, {T}); got {Y.shape}")
+    Y = np.asfortranarray(Y)
+
+    def per_chain(v, name, dtype=np.float64):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            return np.full(T, v, dtype=dtype)
+        if a.shape != (T,):
+            raise ArgumentError(f"`{name}` must be a scalar or have one entry per chain ({T}), got shape {a.shape}")
+        return np.ascontiguousarray(a, dtype=dtype)
+
+    mod = np.array([BAYES_MODELS[m] for m in models], dtype=np.intc)
+    r2, df0 = per_chain(r2, "r2"), per_chain(df0, "df0")
+    prob_in, counts = per_chain(prob_in, "prob_in"), per_chain(counts, "counts")
+    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in per_chain(seeds, "seeds", object)], dtype=np.uint64)
+    b_hat = np.zeros((p + 1, T), order="F")
+    y_pred = np.zeros((n, T), order="F")
+    var = np.zeros((3, T), order="F")
+    pip = np.zeros((p, T), order="F")
+    lib = _lib.load()
+    rc = lib.gbm_bayes_fit_multi(T, _lib.ptr(mod), _lib.ptr(X), n, p, n, _lib.ptr(Y), n, int(n_iter), int(n_burnin),
+                                 int(thin), _lib.ptr(r2), _lib.ptr(df0), _lib.ptr(prob_in), _lib.ptr(counts),
+                                 _lib.ptr(seeds), int(device), _lib.ptr(b_hat), p + 1, _lib.ptr(y_pred), n,
+                                 _lib.ptr(var), _lib.ptr(pip), p)
+    _lib.check(rc, "gbm_bayes_fit_multi")
+    return b_hat, y_pred, var, pip
+
+
 def bayes_ordinal_arrays(model: str, X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500,
                          thin: int = 5, r2: float = 0.5, df0: float = 5.0, prob_in: float = 0.5, counts: float = 10.0,
                          seed: int = 42, device: int = 0, probs: bool = True):
@@ -189,6 +237,69 @@ def _bayes_model_function(model: str, genomes: Genomes, phenomes: Phenomes, idx_
     if not fit.checkdims():
         raise GBMError("Error fitting " + fit.model + ".")
     return fit
+
+
+def bayes_multi_pairs(pairs, genomes: Genomes, phenomes: Phenomes, idx_entries, idx_loci_alleles, n_iter: int,
+                      n_burnin: int, verbose: bool = False):
+    """One Fit per (model, 1-based trait) pair, each what ``bayesa`` / ``bayesb`` / ``bayesc`` returns for the
+    same arguments, from multi-chain fits over one gathered X (32 chains per pass). The traits must have their
+    finite phenotypes on the same entries (one training matrix serves every chain)."""
+    pairs = [(m, int(t)) for m, t in pairs]
+    for m, t in pairs:
+        if m not in BAYES_MODELS:
+            raise ArgumentError(f"model `{m}` is not one of {tuple(BAYES_MODELS)}")
+        if not 1 <= t <= len(phenomes.traits):
+            raise ArgumentError(f"idx_trait = {t} is out of bounds (1 to {len(phenomes.traits)}).")
+    if not pairs:
+        return []
+    traits = list(dict.fromkeys(t for _, t in pairs))
+    X, y0, entries, populations, loci_alleles = extractxyetc(
+        genomes, phenomes, idx_entries=idx_entries, idx_loci_alleles=idx_loci_alleles, idx_trait=traits[0],
+        add_intercept=False)
+    rows = np.arange(len(genomes.entries)) if idx_entries is None else np.asarray(idx_entries, dtype=np.int64) - 1
+    ys = {traits[0]: y0}
+    keep0 = np.isfinite(np.asarray(phenomes.phenotypes[rows, traits[0] - 1], dtype=np.float64))
+    for t in traits[1:]:  # extractxyetc's phenotype handling on the shared rows
+        phi = np.asarray(phenomes.phenotypes[rows, t - 1], dtype=np.float64)
+        if not np.array_equal(np.isfinite(phi), keep0):
+            raise ArgumentError(f"traits `{phenomes.traits[traits[0] - 1]}` and `{phenomes.traits[t - 1]}` have their "
+                                "missing phenotypes on different entries: chains of one pass share the training rows")
+        y = phi[keep0]
+        if y.var(ddof=1) < 1e-20:
+            raise GBMError("Very low or zero variance in trait: `" + str(phenomes.traits[t - 1]) + "`.")
+        ys[t] = y
+    fits = []
+    for c0 in range(0, len(pairs), MAX_CHAINS):
+        chunk = pairs[c0:c0 + MAX_CHAINS]
+        Y = np.column_stack([ys[t] for _, t in chunk])
+        b_hat, y_pred, var, pip = bayes_multi_arrays([m for m, _ in chunk], X, Y, n_iter=n_iter, n_burnin=n_burnin)
+        for c, (m, t) in enumerate(chunk):
+            fit = Fit(n=X.shape[0], l=X.shape[1] + 1)
+            fit.model = m.lower()
+            fit.b_hat_labels = ["intercept"] + list(loci_alleles)
+            fit.trait = phenomes.traits[t - 1]
+            fit.entries = list(entries)
+            fit.populations = list(populations)
+            fit.y_true = ys[t].copy()
+            fit.b_hat = np.ascontiguousarray(b_hat[:, c])
+            fit.y_pred = np.ascontiguousarray(y_pred[:, c])
+            fit.metrics = metrics(fit.y_true, fit.y_pred)
+            if verbose:
+                print(fit.metrics, "posterior means: varE", var[0, c], "mean varB", var[1, c], "pi", var[2, c],
+                      "mean PIP", pip[:, c].mean())
+            if not fit.checkdims():
+                raise GBMError("Error fitting " + fit.model + ".")
+            fits.append(fit)
+    return fits
+
+
+def bayes_multi(models, *, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None,
+                idx_traits=(1,), n_iter: int = 1500, n_burnin: int = 500, verbose: bool = False):
+    """``bayesa`` / ``bayesb`` / ``bayesc`` for every (model, trait) of ``models`` ("BayesA", "BayesB", "BayesC") x
+    ``idx_traits`` (1-based) on one training set, as chains of one pass over its genotypes. Returns the Fits in
+    the order model-major, trait-minor; each equals the model function's Fit for the same arguments."""
+    return bayes_multi_pairs([(m, t) for m in models for t in idx_traits], genomes, phenomes, idx_entries,
+                             idx_loci_alleles, n_iter, n_burnin, verbose)
 
 
 def bayesa(*, genomes: Genomes, phenomes: Phenomes, idx_entries=None, idx_loci_alleles=None, idx_trait: int = 1,

@@ -16,8 +16,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bayes
 from ._lib import ArgumentError, GBMError
+from .bayes import bayesa, bayesb, bayesc
 from .linear import gblup
 from .metrics import metrics
 from .prediction import predict
@@ -77,6 +78,66 @@ def _gblup_lambda(model):
         if not kw or set(kw) <= {"model_label"}:
             return lam
     return None
+
+
+_BAYES_FUNCTIONS = ((bayesa, "BayesA"), (bayesb, "BayesB"), (bayesc, "BayesC"))
+
+
+def _bayes_chain(model):
+    """(model name, n_iter, n_burnin) of a ``bayesa`` / ``bayesb`` / ``bayesc`` model callable (the function, or a
+    ``functools.partial`` of it that sets only ``n_iter`` / ``n_burnin``), else None."""
+    func, kw = (model.func, dict(model.keywords)) if isinstance(model, functools.partial) else (model, {})
+    if isinstance(model, functools.partial) and model.args:
+        return None
+    for f, name in _BAYES_FUNCTIONS:
+        if func is f and set(kw) <= {"n_iter", "n_burnin"}:
+            return name, kw.get("n_iter", 1500), kw.get("n_burnin", 500)
+    return None
+
+
+def _bayes_groups(jobs, cvs, genomes, phenomes):
+    """The BayesA / BayesB / BayesC jobs (i, model, loci) that can share a pass over the genotypes, in lists of at
+    most 32 entries (i, name, trait, rows, loci, n_iter, n_burnin): the same training entries, loci, training
+    rows after the missing-phenotype drop and schedule. Returns (groups, the jobs that share with no other)."""
+    Yall = np.asarray(phenomes.phenotypes, dtype=np.float64)
+    pos_entry = {e: k for k, e in enumerate(genomes.entries)}
+    groups = {}
+    for i, model, loci in jobs:
+        cv = cvs[i]
+        name, n_iter, n_burnin = _bayes_chain(model)
+        rows = np.array([pos_entry[e] for e in cv.fit.entries], dtype=np.int64)
+        trait = phenomes.traits.index(cv.fit.trait)
+        key = (rows.tobytes(), np.asarray(loci, dtype=np.int64).tobytes(), np.isfinite(Yall[rows, trait]).tobytes(),
+               n_iter, n_burnin)
+        groups.setdefault(key, []).append((i, name, trait, rows, loci, n_iter, n_burnin, model))
+    parts, single = [], []
+    for grp in groups.values():
+        if len(grp) == 1:  # nothing to share: the one-model path
+            single.append((grp[0][0], grp[0][7], grp[0][4]))
+            continue
+        parts += [[jb[:7] for jb in grp[g0:g0 + bayes.MAX_CHAINS]] for g0 in range(0, len(grp), bayes.MAX_CHAINS)]
+    return parts, single
+
+
+def _run_bayes_groups(parts, cvs, genomes, phenomes, errors):
+    """Each list of _bayes_groups as one multi-chain fit; every job's Fit is validated as on the one-model path, and
+    an error of the fit is recorded for each of its jobs."""
+    for part in parts:
+        _, _, _, rows, loci, n_iter, n_burnin = part[0]
+        try:
+            fits = bayes.bayes_multi_pairs([(jb[1], jb[2] + 1) for jb in part], genomes, phenomes, list(rows + 1),
+                                           [k + 1 for k in loci], n_iter, n_burnin, False)
+        except (GBMError, ArgumentError) as e:
+            errors.extend((jb[0], str(e)) for jb in part)
+            continue
+        for jb, fit in zip(part, fits):
+            cv = cvs[jb[0]]
+            try:
+                cvs[jb[0]] = validate(fit, genomes, phenomes,
+                                      idx_validation=[genomes.entries.index(e) + 1 for e in cv.validation_entries],
+                                      replication=cv.replication, fold=cv.fold)
+            except (GBMError, ArgumentError) as e:
+                errors.append((jb[0], str(e)))
 
 
 def _model_label(model) -> str:
@@ -172,13 +233,15 @@ def cvmultithread(cvs, *, genomes: Genomes, phenomes: Phenomes, models_vector, v
                   devices=None):
     """Mirror of ``cvmultithread!`` (src/cross_validation.jl:151-207). GBLUP jobs run on one
     genotype session per device (one host thread each), grouped by training set so that the
-    GRM is built once per set and traits sharing a set are solved together; other model
-    callables run as in the reference (called with the six keywords, then ``validate``)."""
+    GRM is built once per set and traits sharing a set are solved together; ``bayesa`` / ``bayesb`` /
+    ``bayesc`` jobs that share a training set, loci and schedule run as chains of one multi-chain fit
+    (``gbm_bayes_fit_multi``, 32 per pass; the CVs are those of the one-model path, bit for bit); other
+    model callables run as in the reference (called with the six keywords, then ``validate``)."""
     if devices is None:
         devices = list(range(max(1, _lib.device_count())))
     pos_loci = {lab: k for k, lab in enumerate(genomes.loci_alleles)}
     pos_entry = {e: k for k, e in enumerate(genomes.entries)}
-    gpu_jobs, other = [], []
+    gpu_jobs, bayes_jobs, other = [], [], []
     Yall = np.asarray(phenomes.phenotypes, dtype=np.float64)
     for i, (cv, model) in enumerate(zip(cvs, models_vector)):
         lam = _gblup_lambda(model)
@@ -187,6 +250,8 @@ def cvmultithread(cvs, *, genomes: Genomes, phenomes: Phenomes, models_vector, v
             gpu_jobs.append(_make_job(i, lam, [pos_entry[e] for e in cv.fit.entries],
                                       [pos_entry[e] for e in cv.validation_entries],
                                       phenomes.traits.index(cv.fit.trait), Yall))
+        elif _bayes_chain(model) is not None:
+            bayes_jobs.append((i, model, loci))
         else:
             other.append((i, model, loci))
     errors, lock = [], threading.Lock()
@@ -216,6 +281,10 @@ def cvmultithread(cvs, *, genomes: Genomes, phenomes: Phenomes, models_vector, v
                 th.join()
             for s in sessions:
                 s.close()
+    if bayes_jobs:
+        parts, single = _bayes_groups(bayes_jobs, cvs, genomes, phenomes)
+        _run_bayes_groups(parts, cvs, genomes, phenomes, errors)
+        other = sorted(other + single, key=lambda jb: jb[0])
     for i, model, loci in other:
         cv = cvs[i]
         try:

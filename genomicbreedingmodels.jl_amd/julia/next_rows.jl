@@ -204,6 +204,45 @@ function bglr_gpu(; G::Matrix{Float64}, y::Vector{Float64}, model::String = "Bay
     b_hat
 end
 
+"""
+    bayes_multi(; G, Y, models, n_iter=1_500, n_burnin=500, thin=5, seeds=fill(UInt64(42), length(models)),
+                device=0, verbose=false)::Matrix{Float64}
+
+`length(models)` (1 to 32) independent BayesA / BayesB / BayesC chains over one `G` in one pass
+(`gbm_bayes_fit_multi`): chain c has the model `models[c]`, the phenotypes `Y[:, c]` and the seed `seeds[c]`, with
+BGLR's default priors. Column c of the result is the vector `bglr_gpu(; G, y=Y[:, c], model=models[c],
+seed=seeds[c], ...)` returns, bit for bit: the models of a cross-validation fold, the traits of a panel or the
+seeds of a convergence check without gathering, uploading and quantising `G` once per fit.
+(This `ccall` has not been run: no Julia where this was written; its argument list is include/gbm.h's.)
+"""
+function bayes_multi(; G::Matrix{Float64}, Y::Matrix{Float64}, models::Vector{String}, n_iter::Int64 = 1_500,
+                     n_burnin::Int64 = 500, thin::Int64 = 5,
+                     seeds::Vector{UInt64} = fill(UInt64(42), length(models)), device::Integer = 0,
+                     verbose::Bool = false)
+    T = length(models)
+    1 <= T <= 32 || throw(ArgumentError("bayes_multi: 1 to 32 chains per call, got $T"))
+    all(m -> haskey(GBM_BAYES_MODELS, m), models) ||
+        throw(ArgumentError("bayes_multi: every model must be BayesA, BayesB or BayesC"))
+    n, p = size(G)
+    size(Y) == (n, T) || throw(ArgumentError("bayes_multi: Y must be $n x $T (one column per chain)"))
+    length(seeds) == T || throw(ArgumentError("bayes_multi: one seed per chain"))
+    codes = Cint[GBM_BAYES_MODELS[m] for m in models]
+    r2, df0, prob_in, counts = fill(0.5, T), fill(5.0, T), fill(0.5, T), fill(10.0, T)
+    b_hat = zeros(p + 1, T)
+    var = zeros(3, T)
+    GC.@preserve G Y codes r2 df0 prob_in counts seeds b_hat var begin
+        rc = ccall((:gbm_bayes_fit_multi, LIBGBM), Cint,
+                   (Int64, Ptr{Cint}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Int64,
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt64}, Cint, Ptr{Float64}, Int64,
+                    Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64),
+                   T, codes, G, n, p, stride(G, 2), Y, stride(Y, 2), n_iter, n_burnin, thin, r2, df0, prob_in, counts,
+                   seeds, device, b_hat, p + 1, C_NULL, n, var, C_NULL, p)
+    end
+    gbm_check(rc, "bayes_multi")
+    verbose && @info "bayes_multi posterior means" models varE = var[1, :] mean_varB = var[2, :] pi = var[3, :]
+    b_hat
+end
+
 # ---- ploidy-aware GRM -----------------------------------------------------------------------
 """
     grmploidyaware_gpu(X::Matrix{Float64}; ploidy=round(Int, 1 / minimum(X[X .!= 0.0])))

@@ -742,6 +742,34 @@ int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx,
                   double* pip_out /* p, may be NULL */);
 
 /*
+ * ---- Several BayesA / BayesB / BayesC chains over one genotype matrix -------------------------
+ * nchains (1 to GBM_BAYES_MAX_CHAINS) independent gbm_bayes_fit chains on the same X in one pass: the
+ * models of a cross-validation fold, the traits of a panel, the seeds of a convergence check. Chain c
+ * has the model models[c], the phenotypes Y[c ldy .. c ldy + n), the priors r2[c], df0[c], prob_in[c],
+ * counts[c] and the seed seeds[c]; the schedule (n_iter, n_burnin, thin) is common. X is uploaded,
+ * quantised and its Gram blocks are built once; every launch of an iteration serves all chains (the
+ * chain launch runs four chains per workgroup, one per wave). (Additive: GBM_VERSION stays 212.)
+ *
+ * Every output of chain c has the bits that gbm_bayes_fit returns for the same model, X, y, priors,
+ * schedule and seed: b_hat_out[c ldb ..] (p+1), y_pred_out[c ldp ..] (n; may be NULL),
+ * var_out[3c ..] (3; may be NULL), pip_out[c ldpip ..] (p; may be NULL).
+ * GBM_E_ARG, before any device work: nchains outside [1, 32]; a NULL among models, X, Y, r2, df0,
+ * prob_in, counts, seeds, b_hat_out; ldy < n, ldb < p + 1, ldp < n, ldpip < p (of the outputs given);
+ * gbm_bayes_fit's checks for every chain, with "chain c" (0-based) in the error text.
+ * Not offered: the ordinal response, BRR, more than 32 chains per call, chains on different
+ * individuals or markers, chain traces.
+ */
+#define GBM_BAYES_MAX_CHAINS 32
+int gbm_bayes_fit_multi(int64_t nchains, const int* models, const double* X, int64_t n, int64_t p, int64_t ldx,
+                        const double* Y, int64_t ldy, int64_t n_iter, int64_t n_burnin, int64_t thin,
+                        const double* r2, const double* df0, const double* prob_in, const double* counts,
+                        const uint64_t* seeds /* each of length nchains */, int device,
+                        double* b_hat_out, int64_t ldb /* (p+1) x nchains */,
+                        double* y_pred_out, int64_t ldp /* n x nchains, may be NULL */,
+                        double* var_out /* 3 x nchains, may be NULL */,
+                        double* pip_out, int64_t ldpip /* p x nchains, may be NULL */);
+
+/*
  * ---- BayesA, BayesB and BayesC with an ordinal response (threshold model) -------------------
  * The reference's bayesian(...; response_type = "ordinal") (src/bayes.jl:28-36, 161-172): BGLR's
  * probit threshold model as restated here (BGLR is not vendored: parity with BGLR itself is
@@ -795,6 +823,8 @@ int gbm_bayes_fit_ordinal(int model, const double* X, int64_t n, int64_t p, int6
  * longer built) and how many fits so far fell back to the per-launch schedule after a sweep
  * hand-off timed out (*fallbacks). */
 int gbm_debug_brr_stats(int* last_path, int64_t* fallbacks);
+/* How many gbm_bayes_fit_multi calls have completed since load and how many chains they ran. */
+int gbm_debug_bayes_multi_stats(int64_t* calls, int64_t* chains);
 /* Chunk shape of the last super-block sweep: C workgroups, the first O own R rows of every
  * super-block and take Ko individuals each, the others Kn. */
 int gbm_debug_brr_shape(int* C, int* O, int* R, int* Ko, int* Kn);

@@ -4,7 +4,11 @@ storage, beside BRR's per-launch path (GBM_BRR_SWEEP=0) on the same box in the s
 per-iteration cost is constant, so two fits of different lengths separate it from the setup
 (upload, column statistics, Gram blocks). ``--response ordinal`` times gbm_bayes_fit_ordinal instead, on the
 same phenotype cut into K = 4 classes at its quartiles (``--response gaussian,ordinal``: both in one run,
-the ratio of the two slopes is the ordinal steps' overhead). Prints one JSON line per measurement."""
+the ratio of the two slopes is the ordinal steps' overhead). ``--chains 1,4,8,24,32`` times gbm_bayes_fit_multi
+with that many chains instead (the models of ``--models`` in turn, one phenotype column and seed per chain) and
+adds the ms per chain-iteration; ``--multi-wg 1`` / ``--multi-wg 4`` force one / four chains per workgroup row
+(GBM_BAYES_MULTI_WG) for the comparison of the two mappings. ``--repeats R`` repeats every measurement (the
+run-to-run spread). Prints one JSON line per measurement."""
 import argparse
 import json
 import os
@@ -35,16 +39,25 @@ def main():
     ap.add_argument("--models", default="BRR,BayesA,BayesB,BayesC")
     ap.add_argument("--storages", default="bytes,fp64")
     ap.add_argument("--response", default="gaussian", help="gaussian, ordinal or both (comma-separated)")
+    ap.add_argument("--chains", default="", help="chain counts of gbm_bayes_fit_multi (comma-separated); empty: none")
+    ap.add_argument("--multi-wg", type=int, default=0, choices=(0, 1, 4),
+                    help="chains per workgroup row of a multi fit (0: the library's choice)")
+    ap.add_argument("--repeats", type=int, default=1)
     args = ap.parse_args()
     import gbm
     from gbm import _lib, synth as S
     X = S.genotypes(4242, args.n, args.p)
-    y = S.qtl_phenotypes(4242, args.n, args.p, ntraits=1)[:, 0]
+    chains = [int(t) for t in args.chains.split(",") if t]
+    Y = S.qtl_phenotypes(4242, args.n, args.p, ntraits=max(chains + [1]))
+    y = np.ascontiguousarray(Y[:, 0])
     lo, hi = max(2, args.iters // 5), args.iters
     cls = np.searchsorted(np.quantile(y, [0.25, 0.5, 0.75]), y).astype(np.float64)  # K = 4
     _lib.debug_set("GBM_BRR_SWEEP", "0")  # BRR: one launch per block, the schedule the chain launches compare with
     for storage in args.storages.split(","):
         _lib.debug_set("GBM_BRR_I8", None if storage == "bytes" else "0")
+        if chains:
+            multi_rows(gbm, _lib, args, chains, X, Y, storage, lo, hi)
+            continue
         for model, response in ((m, r) for m in args.models.split(",") for r in args.response.split(",")):
             if response == "ordinal":
                 if model == "BRR":
@@ -55,16 +68,38 @@ def main():
             else:
                 fit = lambda it, m=model: gbm.bayes_arrays(m, X, y, n_iter=it, n_burnin=it // 2, thin=1)
             fit(2)  # warm-up: the pooled context's buffers
+            for rep in range(args.repeats):
+                ms, s_lo, s_hi, out = per_iteration(fit, lo, hi)
+                launches = -(-args.p // (128 if model == "BRR" and storage == "bytes" else 64))
+                row = {"bench": "Gibbs iteration", "model": model, "response": response, "storage": storage,
+                       "n": args.n, "p": args.p, "iters": [lo, hi], "seconds": [s_lo, s_hi], "ms_per_iter": ms,
+                       "block_launches_per_iter": launches, "us_per_block_launch": ms * 1e3 / launches,
+                       "cor": float(np.corrcoef(out[1], y)[0, 1])}
+                if model != "BRR":
+                    row["pi"] = float(out[2][2])
+                    row["mean_pip"] = float(out[3].mean())
+                print(json.dumps(row), flush=True)
+
+
+def multi_rows(gbm, _lib, args, chains, X, Y, storage, lo, hi):
+    """gbm_bayes_fit_multi at every chain count: the slope per iteration and per chain-iteration."""
+    names = [m for m in args.models.split(",") if m != "BRR"]
+    _lib.debug_set("GBM_BAYES_MULTI_WG", str(args.multi_wg) if args.multi_wg else None)
+    for T in chains:
+        models = [names[c % len(names)] for c in range(T)]
+        Yt = np.asfortranarray(Y[:, :T])
+        fit = lambda it: gbm.bayes_multi_arrays(models, X, Yt, n_iter=it, n_burnin=it // 2, thin=1,
+                                                seeds=[42 + c for c in range(T)])
+        fit(2)  # warm-up: the pooled context's buffers
+        for rep in range(args.repeats):
             ms, s_lo, s_hi, out = per_iteration(fit, lo, hi)
-            launches = -(-args.p // (128 if model == "BRR" and storage == "bytes" else 64))
-            row = {"bench": "Gibbs iteration", "model": model, "response": response, "storage": storage, "n": args.n, "p": args.p,
-                   "iters": [lo, hi], "seconds": [s_lo, s_hi], "ms_per_iter": ms,
-                   "block_launches_per_iter": launches, "us_per_block_launch": ms * 1e3 / launches,
-                   "cor": float(np.corrcoef(out[1], y)[0, 1])}
-            if model != "BRR":
-                row["pi"] = float(out[2][2])
-                row["mean_pip"] = float(out[3].mean())
-            print(json.dumps(row), flush=True)
+            launches = -(-args.p // 64)
+            print(json.dumps({"bench": "Gibbs iteration, multi", "chains": T, "chains_per_workgroup": args.multi_wg,
+                              "models": sorted(set(models)), "storage": storage, "n": args.n, "p": args.p,
+                              "iters": [lo, hi], "seconds": [s_lo, s_hi], "ms_per_iter": ms,
+                              "ms_per_chain_iter": ms / T, "block_launches_per_iter": launches,
+                              "us_per_block_launch": ms * 1e3 / launches,
+                              "cor": float(np.corrcoef(out[1][:, 0], Yt[:, 0])[0, 1])}), flush=True)
 
 
 if __name__ == "__main__":
