@@ -14,24 +14,40 @@
 //
 // gbm_bayes_fit_multi runs up to 32 such chains (a model, phenotype column, priors and seed each) over one X
 // in one pass: the same kernels with a chain index, each chain's bits those of gbm_bayes_fit.
+// gbm_bayes_fit_multi_rows gives each chain a set of training rows of that X (the folds of a cross-validation):
+// the SETS instantiations of the kernels, per-set column statistics and Gram blocks.
 #include "gibbs_common.h"
 
 namespace gbm {
 namespace {
 
-// the intercept step of brr_mu_kernel on the stream A = 8 it; workgroup c is chain c (e at c·lde, state c)
+// the intercept step of brr_mu_kernel on the stream A = 8 it; workgroup c is chain c (e at c·lde, state c).
+// SETS (gbm_bayes_fit_multi_rows): over the chain's n_c training rows; a held-out row adds 0.0 to the sum in its
+// place and its e stays 0.0.
+template <bool SETS>
 __global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, int64_t lde, int64_t n,
-                                                        BayesState* __restrict__ st) {
+                                                        BayesState* __restrict__ st, RowSetsArg<SETS> rs) {
   __shared__ double red[16];
   e += (int64_t)blockIdx.x * lde;
   st += blockIdx.x;
   const double mu_old = st->mu;
   double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 1024) s += e[i] + mu_old;
+  int64_t nc = n;  // the individuals in the mean
+  if constexpr (SETS) {
+    nc = rs.nrows[blockIdx.x];
+    for (int64_t i = threadIdx.x; i < n; i += 1024) s += (rs.mask[i] >> blockIdx.x) & 1u ? e[i] + mu_old : 0.0;
+  } else {
+    for (int64_t i = threadIdx.x; i < n; i += 1024) s += e[i] + mu_old;
+  }
   s = brr_block_sum<1024>(s, red);
   const double varE = st->varE;
-  const double mu = s / (double)n + sqrt(varE / (double)n) * brr_normal(st->seed, 8 * (uint64_t)st->it, 0xFFFFFFFFull);
-  for (int64_t i = threadIdx.x; i < n; i += 1024) e[i] = (e[i] + mu_old) - mu;
+  const double mu = s / (double)nc + sqrt(varE / (double)nc) * brr_normal(st->seed, 8 * (uint64_t)st->it, 0xFFFFFFFFull);
+  if constexpr (SETS) {
+    for (int64_t i = threadIdx.x; i < n; i += 1024)
+      if ((rs.mask[i] >> blockIdx.x) & 1u) e[i] = (e[i] + mu_old) - mu;
+  } else {
+    for (int64_t i = threadIdx.x; i < n; i += 1024) e[i] = (e[i] + mu_old) - mu;
+  }
   __syncthreads();
   if (threadIdx.x == 0) st->mu = mu;
 }
@@ -41,14 +57,17 @@ __global__ void __launch_bounds__(1024) bayes_mu_kernel(double* __restrict__ e, 
 //   5: b/(2 varE)   6: −b x2   7: log(π/(1−π)) − logit(u)
 // so that with r = x_jᵀe + x2 eff:  logOdds − logit(u) = pk5 (2 r + pk6) + pk7,  b_in = a r + c.
 // BayesA: pk5 = pk6 = 0, pk7 = 1 (always included). blockIdx.y is the chain (x2 is common; b and d at
-// c·2p, varB at c·p, pk at c·8·ppad, state c).
+// c·2p, varB at c·p, pk at c·8·ppad, state c). SETS: x2 of the chain's set, at set·p.
+template <bool SETS>
 __global__ void __launch_bounds__(256) bayes_prep_kernel(int64_t p, int64_t ppad, const double* __restrict__ x2,
                                                          const double* __restrict__ b, const double* __restrict__ d,
                                                          const double* __restrict__ varB,
-                                                         const BayesState* __restrict__ st, double* __restrict__ pk) {
+                                                         const BayesState* __restrict__ st, double* __restrict__ pk,
+                                                         RowSetsArg<SETS> rs) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= ppad) return;
   const int64_t ch = blockIdx.y;
+  if constexpr (SETS) x2 += rs.set_of[ch] * p;
   b += ch * 2 * p;
   d += ch * 2 * p;
   varB += ch * p;
@@ -99,7 +118,13 @@ __global__ void __launch_bounds__(256) bayes_prep_kernel(int64_t p, int64_t ppad
 // neighbours. Chain c's buffers: e at c·ldx, b and d at c·2p, the running means at c·p, pk at
 // c·8·64·nblk, its ping-pong partials at c·2·64·chunks, state c. ROWS = false (CH = 1, one chain: the
 // launch of gbm_bayes_fit) compiles the chain index out.
-template <typename T, int CH, bool ROWS>
+//
+// SETS (gbm_bayes_fit_multi_rows): chain c trains on the individuals whose mask word has bit c. Its e is exactly
+// 0.0 on the others (the start value is, and e += X_B δ is skipped there by a select), so every dot x_jᵀe (d⁰, the
+// next block's partials, Σe²) runs unchanged: a held-out individual adds an exact zero in its place of the fixed
+// order. The running wave loads its W column from its chain's set (W at set·wstride). One mask load per thread
+// serves the row's chains.
+template <typename T, int CH, bool ROWS, bool SETS = false>
 __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ Xt, int64_t ldx, int64_t n,
                                                           int64_t p, double xs, const double* __restrict__ W,
                                                           int64_t blk, int64_t nblk, int nch,
@@ -108,7 +133,8 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
                                                           const double* __restrict__ pk, double* __restrict__ b,
                                                           double* __restrict__ d, double* __restrict__ bbar,
                                                           double* __restrict__ dbar, double* __restrict__ e,
-                                                          const BayesState* __restrict__ st) {
+                                                          const BayesState* __restrict__ st,
+                                                          RowSetsArg<SETS> rs) {
   constexpr int RP = IW + 2;  // doubles (row pitch 2064 B, as brr_step_kernel)
   __shared__ __attribute__((aligned(16))) double Xn[BB * RP];
   __shared__ double delta[CH][BB];
@@ -116,6 +142,7 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
   __shared__ double part4[CH][4][BB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   static_assert(ROWS || CH == 1, "a launch without chain rows runs one chain");
+  static_assert(ROWS || !SETS, "training sets come with chain rows");
   const int ch0 = ROWS ? (int)blockIdx.y * CH : 0;                 // the row's first chain
   const int nc = ROWS ? (nch - ch0 < CH ? nch - ch0 : CH) : 1;     // its chains (>= 1)
   const int mine = CH == 1 ? 0 : wave;                     // the slot whose chain this wave runs
@@ -156,6 +183,8 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
   double e_old[CH];
 #pragma unroll
   for (int c = 0; c < CH; c++) e_old[c] = c < nc ? e[(ch0 + c) * ldx + i] : 0.0;
+  [[maybe_unused]] uint32_t trains = 0;  // bit c: this thread's individual trains chain ch0 + c
+  if constexpr (SETS) trains = rs.mask[i] >> ch0;
   // (3) a running wave's operands: column `lane` of W (= its row: W is symmetric) and the step constants
   double w[BB];
   double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -163,6 +192,7 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
   const int64_t j = j0 + lane;
   if (runner) {
     const double* wr = W + (blk * BB + lane) * BB;
+    if constexpr (SETS) wr += rs.set_of[ch] * rs.wstride;
 #pragma unroll
     for (int s = 0; s < BB; s += 2) {
       const double2 v = *reinterpret_cast<const double2*>(wr + s);
@@ -237,6 +267,7 @@ __global__ void __launch_bounds__(256) bayes_chain_kernel(const T* __restrict__ 
         acc1 = fma(delta[c][s2 + 1], xv[s2 + 1], acc1);
       }
       ei[c] = e_old[c] + (acc0 + acc1);
+      if constexpr (SETS) ei[c] = (trains >> c) & 1u ? ei[c] : 0.0;
       e[(ch0 + c) * ldx + i] = ei[c];
     }
   }
@@ -324,12 +355,15 @@ __global__ void __launch_bounds__(256) bayes_var_kernel(const double* __restrict
 }
 
 // The scalar draws of an iteration (one workgroup): S, BayesC's common varB, π, varE; the running
-// means of μ, varE, mean_j varB_j and π; next iteration. Workgroup c is chain c.
+// means of μ, varE, mean_j varB_j and π; next iteration. Workgroup c is chain c. SETS: n is the chain's n_c.
+template <bool SETS>
 __global__ void __launch_bounds__(256) bayes_final_kernel(const double* __restrict__ vpart, int64_t nvb, int64_t p,
-                                                          int64_t n, BayesState* __restrict__ st) {
+                                                          int64_t n, BayesState* __restrict__ st,
+                                                          RowSetsArg<SETS> rs) {
   __shared__ double red[4];
   vpart += (int64_t)blockIdx.x * 5 * nvb;
   st += blockIdx.x;
+  if constexpr (SETS) n = rs.nrows[blockIdx.x];
   double sum[5];
 #pragma unroll
   for (int u = 0; u < 5; u++) {
@@ -389,7 +423,8 @@ int bayes_check_args(const char* entry, int model, const double* X, const double
   return GBM_OK;
 }
 
-int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, int64_t nchains, GibbsData& g) {
+int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, int64_t nchains, GibbsData& g,
+                       RowSetsHost* rs) {
   const int dev = cx.dev;
   const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB, T = nchains;
   const int64_t npad = round_up(n, IW), C = (n + IW - 1) / IW;
@@ -404,7 +439,12 @@ int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_
     GBM_TRY(ensure(cx.bbar, dev, T * p * 8));
     GBM_TRY(ensure(cx.r, dev, std::max<int64_t>(T * 2 * C * BB, 2 * C * BK2) * 8));
   }
+  if (rs) {  // the per-set sizes first, so that gibbs_upload's own ensure finds them
+    GBM_TRY(ensure(cx.colmean, dev, rs->nsets * p * 8));
+    GBM_TRY(ensure(cx.x2, dev, rs->nsets * p * 8));
+  }
   GBM_TRY(gibbs_upload(cx, X, n, p, ldx, g));
+  if (rs) return gibbs_sets(cx, n, p, g.npad, nblk, nchains, *rs);
   GBM_TRY(gibbs_gram(cx, n, p, g.npad, nblk, 1));
   GBM_HIP_TRY(hipStreamSynchronize(cx.stream.s));
   return GBM_OK;
@@ -413,10 +453,15 @@ int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_
 int bayes_start(const char* entry, BrrCtx& cx, int64_t chain, int model, int64_t n, int64_t p, const double* y,
                 int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts, uint64_t seed,
                 const GibbsData& g, BayesState& st0) {
-  hipStream_t s = cx.stream.s;
-  const int64_t npad = g.npad;
   GibbsPrior pr;
   GBM_TRY(gibbs_prior(entry, y, n, p, g, pr));
+  return bayes_start_from(cx, chain, model, p, g.npad, pr, n_burnin, thin, r2, df0, prob_in, counts, seed, st0);
+}
+
+int bayes_start_from(BrrCtx& cx, int64_t chain, int model, int64_t p, int64_t npad, const GibbsPrior& pr,
+                     int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
+                     uint64_t seed, BayesState& st0) {
+  hipStream_t s = cx.stream.s;
   const double shape0 = 1.1;
   double S0 = pr.vy * r2 / pr.msx * (df0 + 2.0);
   if (model != GBM_BAYES_A) S0 /= prob_in;
@@ -460,32 +505,48 @@ int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64
 }
 
 namespace {
-template <typename T, int CH, bool ROWS>
+template <typename T, int CH, bool ROWS, bool SETS = false>
 void launch_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, int64_t k, int64_t nblk, int64_t nchains,
-                  BayesState* stp) {
+                  BayesState* stp, RowSetsArg<SETS> rs = {}) {
   const int64_t C = g.C64;
   const T* X = sizeof(T) == 8 ? (const T*)cx.Xt.p : (const T*)cx.D.p;
   const double* pin = (const double*)cx.r.p + (k & 1) * C * BB;
   double* pout = (double*)cx.r.p + ((k + 1) & 1) * C * BB;
-  bayes_chain_kernel<T, CH, ROWS><<<dim3((unsigned)C, (unsigned)((nchains + CH - 1) / CH)), 256, 0, cx.stream.s>>>(
+  bayes_chain_kernel<T, CH, ROWS, SETS><<<dim3((unsigned)C, (unsigned)((nchains + CH - 1) / CH)), 256, 0, cx.stream.s>>>(
       X, g.npad, n, p, sizeof(T) == 8 ? 1.0 : g.xs, (const double*)cx.W.p, k, nblk, (int)nchains, pin, pout,
       (const double*)cx.pk.p, (double*)cx.b.p, (double*)cx.dind.p, (double*)cx.bbar.p, (double*)cx.dbar.p,
-      (double*)cx.e.p, stp);
+      (double*)cx.e.p, stp, rs);
 }
 }  // namespace
 
 void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* stp, int64_t nchains,
-                         int per_wg) {
+                         int per_wg, const RowSets* rs) {
   hipStream_t s = cx.stream.s;
   const int64_t nblk = (p + BB - 1) / BB, ppad = nblk * BB;
   const bool bytes = g.xs > 0.0;
-  bayes_prep_kernel<<<dim3((unsigned)(ppad / 256 + 1), (unsigned)nchains), 256, 0, s>>>(
-      p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p, (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
-      (double*)cx.pk.p);
-  bayes_mu_kernel<<<(unsigned)nchains, 1024, 0, s>>>((double*)cx.e.p, g.npad, n, stp);
+  const dim3 pgrid((unsigned)(ppad / 256 + 1), (unsigned)nchains);
+  if (rs) {
+    bayes_prep_kernel<true><<<pgrid, 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
+                                                  (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
+                                                  (double*)cx.pk.p, *rs);
+    bayes_mu_kernel<true><<<(unsigned)nchains, 1024, 0, s>>>((double*)cx.e.p, g.npad, n, stp, *rs);
+  } else {
+    bayes_prep_kernel<false><<<pgrid, 256, 0, s>>>(p, ppad, (const double*)cx.x2.p, (const double*)cx.b.p,
+                                                   (const double*)cx.dind.p, (const double*)cx.varBj.p, stp,
+                                                   (double*)cx.pk.p, NoRowSets{});
+    bayes_mu_kernel<false><<<(unsigned)nchains, 1024, 0, s>>>((double*)cx.e.p, g.npad, n, stp, NoRowSets{});
+  }
   gibbs_dots0(cx, n, p, g, bytes, nchains);
   for (int64_t k = 0; k < nblk; k++) {
-    if (per_wg == 4) {
+    if (rs) {  // held-out rows: e stays 0.0 there (one chain per row also when there is one chain)
+      if (per_wg == 4) {
+        if (bytes) launch_chain<uint8_t, 4, true, true>(cx, n, p, g, k, nblk, nchains, stp, *rs);
+        else launch_chain<double, 4, true, true>(cx, n, p, g, k, nblk, nchains, stp, *rs);
+      } else {
+        if (bytes) launch_chain<uint8_t, 1, true, true>(cx, n, p, g, k, nblk, nchains, stp, *rs);
+        else launch_chain<double, 1, true, true>(cx, n, p, g, k, nblk, nchains, stp, *rs);
+      }
+    } else if (per_wg == 4) {
       if (bytes) launch_chain<uint8_t, 4, true>(cx, n, p, g, k, nblk, nchains, stp);
       else launch_chain<double, 4, true>(cx, n, p, g, k, nblk, nchains, stp);
     } else if (nchains > 1) {
@@ -536,7 +597,7 @@ static int bayes_fit_impl(int model, const double* X, int64_t n, int64_t p, int6
   auto enqueue_iteration = [&]() -> int {
     bayes_enqueue_chain(cx, n, p, g, stp);
     bayes_enqueue_var(cx, n, p, stp);
-    bayes_final_kernel<<<1, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp);
+    bayes_final_kernel<false><<<1, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp, NoRowSets{});
     return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, "gbm_bayes_fit: launch failed");
   };
   cx.bayes_graph.ensure({model, n, p, npad, (int64_t)(xs * 64.0), key_of(cx.Xt), key_of(cx.D), key_of(cx.W),
@@ -572,13 +633,18 @@ extern "C" int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, i
 // gbm_bayes_fit_multi on a leased context: gbm_bayes_fit's setup once (genotypes, column statistics, byte
 // quantisation, Gram blocks), a start state per chain, then the iteration of all chains (the kernels of
 // gbm_bayes_fit with a chain index) captured as the context's multi graph and replayed; outputs per chain.
-static std::atomic<int64_t> g_multi_calls{0}, g_multi_chains{0};
+// rsh (gbm_bayes_fit_multi_rows): chain c trains on the rows of its set. The statistics and Gram blocks are built
+// per set, the prior moments and the start residual are taken over the set, and the iteration is that of the SETS
+// kernels, captured in a graph slot of its own (the key holds nsets and the mask buffers).
+static std::atomic<int64_t> g_multi_calls{0}, g_multi_chains{0}, g_rows_calls{0}, g_rows_chains{0};
 
 static int bayes_fit_multi_impl(int64_t T, const int* models, const double* X, int64_t n, int64_t p, int64_t ldx,
                                 const double* Y, int64_t ldy, int64_t n_iter, int64_t n_burnin, int64_t thin,
                                 const double* r2, const double* df0, const double* prob_in, const double* counts,
                                 const uint64_t* seeds, int dev, double* b_hat_out, int64_t ldb, double* y_pred_out,
-                                int64_t ldp, double* var_out, double* pip_out, int64_t ldpip) {
+                                int64_t ldp, double* var_out, double* pip_out, int64_t ldpip,
+                                RowSetsHost* rsh = nullptr) {
+  const char* entry = rsh ? "gbm_bayes_fit_multi_rows" : "gbm_bayes_fit_multi";
   BrrLease lease;
   GBM_TRY(CtxPool<BrrCtx>::instance().acquire(dev, lease.c));
   BrrCtx& cx = *lease.c;
@@ -586,14 +652,36 @@ static int bayes_fit_multi_impl(int64_t T, const int* models, const double* X, i
   hipStream_t s = cx.stream.s;
   GBM_TRY(ensure(cx.bst, dev, T * (int64_t)sizeof(BayesState)));
   GibbsData g;
-  GBM_TRY(bayes_setup_shared(cx, X, n, p, ldx, T, g));
-  std::vector<BayesState> st0((size_t)T);
-  for (int64_t c = 0; c < T; c++) {
-    const std::string who = "gbm_bayes_fit_multi: chain " + std::to_string(c);
-    GBM_TRY(bayes_start(who.c_str(), cx, c, models[c], n, p, Y + c * ldy, n_burnin, thin, r2[c], df0[c], prob_in[c],
-                        counts[c], seeds[c], g, st0[(size_t)c]));
-  }
+  GBM_TRY(bayes_setup_shared(cx, X, n, p, ldx, T, g, rsh));
   const int64_t npad = g.npad, nvb = bayes_var_blocks(n, p);
+  std::vector<BayesState> st0((size_t)T);
+  if (rsh) {
+    GibbsPrior pr;
+    for (int64_t t = 0; t < rsh->nsets; t++) {  // MSx of every set, named by set
+      double msx = 0.0, smsq = 0.0;
+      for (int64_t j = 0; j < p; j++) {
+        msx += rsh->xx[(size_t)(t * p + j)];
+        smsq += rsh->cm[(size_t)(t * p + j)] * rsh->cm[(size_t)(t * p + j)];
+      }
+      if (!(msx / (double)rsh->nrows[(size_t)t] - smsq > 0.0))
+        return fail(GBM_E_DATA, std::string(entry) + ": set " + std::to_string(t) +
+                                    ": the markers have no variance on its rows");
+    }
+    for (int64_t c = 0; c < T; c++) {
+      const std::string who = std::string(entry) + ": chain " + std::to_string(c);
+      const int64_t t = rsh->set_of[c];
+      GBM_TRY(gibbs_prior_rows(who.c_str(), Y + c * ldy, n, p, npad, rsh->rows + t * rsh->ldrows,
+                               rsh->nrows[(size_t)t], rsh->cm.data() + t * p, rsh->xx.data() + t * p, pr));
+      GBM_TRY(bayes_start_from(cx, c, models[c], p, npad, pr, n_burnin, thin, r2[c], df0[c], prob_in[c], counts[c],
+                               seeds[c], st0[(size_t)c]));
+    }
+  } else {
+    for (int64_t c = 0; c < T; c++) {
+      const std::string who = "gbm_bayes_fit_multi: chain " + std::to_string(c);
+      GBM_TRY(bayes_start(who.c_str(), cx, c, models[c], n, p, Y + c * ldy, n_burnin, thin, r2[c], df0[c], prob_in[c],
+                          counts[c], seeds[c], g, st0[(size_t)c]));
+    }
+  }
   GBM_HIP_TRY(hipMemcpyAsync(cx.bst.p, st0.data(), (size_t)T * sizeof(BayesState), hipMemcpyHostToDevice, s));
   GBM_HIP_TRY(hipStreamSynchronize(s));
   auto* stp = (BayesState*)cx.bst.p;
@@ -609,17 +697,24 @@ static int bayes_fit_multi_impl(int64_t T, const int* models, const double* X, i
   const int64_t rounds1 = (g.C64 * T + cus - 1) / cus, rounds4 = (g.C64 * ((T + 3) / 4) + cus - 1) / cus;
   const int64_t forced = knob_i64("GBM_BAYES_MULTI_WG", 0);
   const int per_wg = forced == 1 ? 1 : forced == 4 ? 4 : (rounds1 <= 2 * rounds4 ? 1 : 4);
+  const RowSets rs{(const uint32_t*)cx.smask.p, (const int*)cx.sof.p, (const int64_t*)cx.snrows.p,
+                   ((p + BB - 1) / BB) * BB * BB};  // read by the SETS launches only
   auto enqueue_iteration = [&]() -> int {
-    bayes_enqueue_chain(cx, n, p, g, stp, T, per_wg);
+    bayes_enqueue_chain(cx, n, p, g, stp, T, per_wg, rsh ? &rs : nullptr);
     bayes_enqueue_var(cx, n, p, stp, T);
-    bayes_final_kernel<<<(unsigned)T, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp);
-    return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, "gbm_bayes_fit_multi: launch failed");
+    if (rsh)
+      bayes_final_kernel<true><<<(unsigned)T, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp, rs);
+    else
+      bayes_final_kernel<false><<<(unsigned)T, 256, 0, s>>>((const double*)cx.vpart.p, nvb, p, n, stp, NoRowSets{});
+    return hipGetLastError() == hipSuccess ? GBM_OK : fail(GBM_E_HIP, std::string(entry) + ": launch failed");
   };
-  cx.multi_graph.ensure({T, per_wg, n, p, npad, (int64_t)(g.xs * 64.0), key_of(cx.Xt), key_of(cx.D), key_of(cx.W),
-                         key_of(cx.r), key_of(cx.e), key_of(cx.b), key_of(cx.dind), key_of(cx.bbar), key_of(cx.dbar),
-                         key_of(cx.varBj), key_of(cx.pk), key_of(cx.vpart), key_of(cx.x2), key_of(cx.bst)},
-                        s, enqueue_iteration);
-  GBM_TRY(cx.multi_graph.run(n_iter, s, "gbm_bayes_fit_multi", enqueue_iteration));
+  std::vector<int64_t> key{T, per_wg, n, p, npad, (int64_t)(g.xs * 64.0), key_of(cx.Xt), key_of(cx.D), key_of(cx.W),
+                           key_of(cx.r), key_of(cx.e), key_of(cx.b), key_of(cx.dind), key_of(cx.bbar), key_of(cx.dbar),
+                           key_of(cx.varBj), key_of(cx.pk), key_of(cx.vpart), key_of(cx.x2), key_of(cx.bst)};
+  if (rsh) key.insert(key.end(), {rsh->nsets, key_of(cx.smask), key_of(cx.sof), key_of(cx.snrows)});
+  IterGraph& graph = rsh ? cx.rows_graph : cx.multi_graph;
+  graph.ensure(key, s, enqueue_iteration);
+  GBM_TRY(graph.run(n_iter, s, entry, enqueue_iteration));
   for (int64_t c = 0; c < T; c++) {
     BayesState fin{};
     GBM_TRY(gibbs_outputs(cx, n, p, npad, cx.bst, &fin, sizeof(fin), &fin.mubar, b_hat_out + c * ldb,
@@ -630,8 +725,23 @@ static int bayes_fit_multi_impl(int64_t T, const int* models, const double* X, i
       var_out[3 * c + 2] = fin.pibar;
     }
   }
-  g_multi_calls.fetch_add(1, std::memory_order_relaxed);
-  g_multi_chains.fetch_add(T, std::memory_order_relaxed);
+  (rsh ? g_rows_calls : g_multi_calls).fetch_add(1, std::memory_order_relaxed);
+  (rsh ? g_rows_chains : g_multi_chains).fetch_add(T, std::memory_order_relaxed);
+  return GBM_OK;
+}
+
+// the checks of the chain count, the required pointers and the pitches that both multi-chain entries make first
+static int multi_check_shape(const char* entry, int64_t nchains, const int* models, const double* X, const double* Y,
+                             const double* r2, const double* df0, const double* prob_in, const double* counts,
+                             const uint64_t* seeds, const double* b_hat_out, int64_t n, int64_t p, int64_t ldy,
+                             int64_t ldb, const double* y_pred_out, int64_t ldp, const double* pip_out, int64_t ldpip) {
+  const std::string who(entry);
+  if (nchains < 1 || nchains > GBM_BAYES_MAX_CHAINS)
+    return fail(GBM_E_ARG, who + ": 1 <= nchains <= " + std::to_string(GBM_BAYES_MAX_CHAINS));
+  if (!models || !X || !Y || !r2 || !df0 || !prob_in || !counts || !seeds || !b_hat_out)
+    return fail(GBM_E_ARG, who + ": models, X, Y, r2, df0, prob_in, counts, seeds and b_hat_out are required");
+  if (ldy < n || ldb < p + 1 || (y_pred_out && ldp < n) || (pip_out && ldpip < p))
+    return fail(GBM_E_ARG, who + ": bad pitch (ldy >= n, ldb >= p + 1, ldp >= n, ldpip >= p)");
   return GBM_OK;
 }
 
@@ -643,12 +753,8 @@ extern "C" int gbm_bayes_fit_multi(int64_t nchains, const int* models, const dou
                                    int64_t ldpip) {
   RoctxRange r_("gbm_bayes_fit_multi");
   set_error("");
-  if (nchains < 1 || nchains > GBM_BAYES_MAX_CHAINS)
-    return fail(GBM_E_ARG, "gbm_bayes_fit_multi: 1 <= nchains <= " + std::to_string(GBM_BAYES_MAX_CHAINS));
-  if (!models || !X || !Y || !r2 || !df0 || !prob_in || !counts || !seeds || !b_hat_out)
-    return fail(GBM_E_ARG, "gbm_bayes_fit_multi: models, X, Y, r2, df0, prob_in, counts, seeds and b_hat_out are required");
-  if (ldy < n || ldb < p + 1 || (y_pred_out && ldp < n) || (pip_out && ldpip < p))
-    return fail(GBM_E_ARG, "gbm_bayes_fit_multi: bad pitch (ldy >= n, ldb >= p + 1, ldp >= n, ldpip >= p)");
+  GBM_TRY(multi_check_shape("gbm_bayes_fit_multi", nchains, models, X, Y, r2, df0, prob_in, counts, seeds, b_hat_out,
+                            n, p, ldy, ldb, y_pred_out, ldp, pip_out, ldpip));
   int dev = 0;
   for (int64_t c = 0; c < nchains; c++) {
     const std::string who = "gbm_bayes_fit_multi: chain " + std::to_string(c);
@@ -661,6 +767,68 @@ extern "C" int gbm_bayes_fit_multi(int64_t nchains, const int* models, const dou
   GBM_TRY(gibbs_check_run("gbm_bayes_fit_multi", Y, n, n_iter, n_burnin, thin, device, dev));
   return bayes_fit_multi_impl(nchains, models, X, n, p, ldx, Y, ldy, n_iter, n_burnin, thin, r2, df0, prob_in, counts,
                               seeds, dev, b_hat_out, ldb, y_pred_out, ldp, var_out, pip_out, ldpip);
+}
+
+extern "C" int gbm_bayes_fit_multi_rows(int64_t nchains, const int* models, const double* X, int64_t n, int64_t p,
+                                        int64_t ldx, const double* Y, int64_t ldy, int64_t nsets, const uint8_t* rows,
+                                        int64_t ldrows, const int* set_of, int64_t n_iter, int64_t n_burnin,
+                                        int64_t thin, const double* r2, const double* df0, const double* prob_in,
+                                        const double* counts, const uint64_t* seeds, int device, double* b_hat_out,
+                                        int64_t ldb, double* y_pred_out, int64_t ldp, double* var_out, double* pip_out,
+                                        int64_t ldpip) {
+  const char* entry = "gbm_bayes_fit_multi_rows";
+  RoctxRange r_(entry);
+  set_error("");
+  const std::string who(entry);
+  GBM_TRY(multi_check_shape(entry, nchains, models, X, Y, r2, df0, prob_in, counts, seeds, b_hat_out, n, p, ldy, ldb,
+                            y_pred_out, ldp, pip_out, ldpip));
+  if (nsets < 1 || nsets > nchains) return fail(GBM_E_ARG, who + ": 1 <= nsets <= nchains");
+  if (!rows || !set_of) return fail(GBM_E_ARG, who + ": rows and set_of are required");
+  if (n < 3 || ldx < n || ldrows < n) return fail(GBM_E_ARG, who + ": bad arguments (n >= 3, ldx >= n, ldrows >= n)");
+  RowSetsHost rsh;
+  rsh.nsets = nsets;
+  rsh.rows = rows;
+  rsh.ldrows = ldrows;
+  rsh.set_of = set_of;
+  rsh.nrows.assign((size_t)nsets, 0);
+  for (int64_t t = 0; t < nsets; t++) {
+    const uint8_t* r = rows + t * ldrows;
+    int64_t nc = 0;
+    for (int64_t i = 0; i < n; i++) {
+      if (r[i] > 1)
+        return fail(GBM_E_ARG, who + ": set " + std::to_string(t) + " has a byte other than 0 or 1 at row " +
+                                   std::to_string(i));
+      nc += r[i];
+    }
+    if (nc < 3) return fail(GBM_E_ARG, who + ": set " + std::to_string(t) + " has fewer than 3 rows");
+    rsh.nrows[(size_t)t] = nc;
+  }
+  std::vector<double> ys;
+  for (int64_t c = 0; c < nchains; c++) {
+    const std::string whoc = who + ": chain " + std::to_string(c);
+    if (set_of[c] < 0 || set_of[c] >= nsets)
+      return fail(GBM_E_ARG, whoc + ": set_of is " + std::to_string(set_of[c]) + ", outside [0, nsets)");
+    const uint8_t* r = rows + set_of[c] * ldrows;
+    const int64_t nc = rsh.nrows[(size_t)set_of[c]];
+    // gbm_bayes_fit's checks with the chain's own n_c (ldx >= n is checked above)
+    GBM_TRY(bayes_check_args(whoc.c_str(), models[c], X, Y + c * ldy, b_hat_out, nc, p, nc, n_iter, n_burnin, thin,
+                             r2[c], df0[c], prob_in[c], counts[c]));
+    ys.clear();  // the phenotype checks on the chain's rows: Y is not read as a number elsewhere
+    for (int64_t i = 0; i < n; i++)
+      if (r[i]) ys.push_back(Y[c * ldy + i]);
+    const int rc = check_y(ys.data(), nc, nc, 1);  // its "entry k" is the k-th row of the set
+    if (rc != GBM_OK) return fail(rc, whoc + ": " + last_error());
+  }
+  int dev = 0;
+  GBM_TRY(gibbs_check_run(entry, nullptr, n, n_iter, n_burnin, thin, device, dev));
+  return bayes_fit_multi_impl(nchains, models, X, n, p, ldx, Y, ldy, n_iter, n_burnin, thin, r2, df0, prob_in, counts,
+                              seeds, dev, b_hat_out, ldb, y_pred_out, ldp, var_out, pip_out, ldpip, &rsh);
+}
+
+extern "C" int gbm_debug_bayes_rows_stats(int64_t* calls, int64_t* chains) {
+  if (calls) *calls = g_rows_calls.load(std::memory_order_relaxed);
+  if (chains) *chains = g_rows_chains.load(std::memory_order_relaxed);
+  return GBM_OK;
 }
 
 extern "C" int gbm_debug_bayes_multi_stats(int64_t* calls, int64_t* chains) {

@@ -3,7 +3,8 @@
 //   brr.hip          Bayesian ridge regression: the per-launch kernels, gbm_brr_fit, the debug exports;
 //   brr_sweep.hip    its persistent super-block sweep, behind brr_sweep_plan / _setup / _enqueue;
 //   bayes_abc.hip    BayesA, BayesB, BayesC: gbm_bayes_fit, gbm_bayes_fit_multi (several chains over one X),
-//                    and the steps the ordinal fit replays;
+//                    gbm_bayes_fit_multi_rows (each chain on its own rows of X), and the steps the ordinal fit
+//                    replays;
 //   bayes_ordinal.hip  their ordinal (threshold-model) response: gbm_bayes_fit_ordinal.
 //
 // Random numbers: a counter-based hash of (seed, stream, counter) (no sampler state), Box-Muller
@@ -12,6 +13,7 @@
 #pragma once
 #include <functional>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "counter_hash.h"
@@ -145,6 +147,17 @@ struct OrdinalState {
   double tbar[ORD_MAXK + 1];  // running means of t_1 … t_{K−1} (entry k)
   int64_t K;
 };
+// gbm_bayes_fit_multi_rows: what the chains' training rows add to a kernel's arguments (SETS instantiations only;
+// the others take the empty NoRowSets and compile as before)
+struct RowSets {
+  const uint32_t* mask;  // npad words: bit c set when the individual trains chain c (0 past n)
+  const int* set_of;     // nchains: the chain's set
+  const int64_t* nrows;  // nchains: n_c, the size of the chain's set
+  int64_t wstride;       // doubles between two sets' Gram blocks
+};
+struct NoRowSets {};
+template <bool SETS>
+using RowSetsArg = std::conditional_t<SETS, RowSets, NoRowSets>;
 // the sample gate: does this iteration enter the running posterior means?
 template <typename State>
 __device__ __forceinline__ bool brr_accumulate(const State* st) {
@@ -242,8 +255,11 @@ __device__ __forceinline__ void brr_partials(const T* __restrict__ Xt, int64_t l
 // One 64x64 tile X_RᵀX_C of a Gram matrix for the marker rows R = [r0, r0 + 64), C = [c0, c0 + 64) of
 // Xt (rows past p are zero), by one 256-thread workgroup: individuals in chunks of 64 staged through
 // LDS, thread (a, b0) sums out[a][b0 .. b0 + 15]. out: the tile's first element, row pitch ldo.
+// SETS: over a set of individuals, rows[i] != 0 (n of them readable); the others enter as 0.0 in the same order.
+template <bool SETS = false>
 __device__ __forceinline__ void brr_gram_tile(const double* __restrict__ Xt, int64_t ldx, int64_t p, int64_t n,
-                                              int64_t r0, int64_t c0, double* __restrict__ out, int64_t ldo) {
+                                              int64_t r0, int64_t c0, double* __restrict__ out, int64_t ldo,
+                                              const uint8_t* __restrict__ rows = nullptr) {
   __shared__ double TR[BB][BB + 1];
   __shared__ double TC[BB][BB + 1];
   const int tid = threadIdx.x, a = tid >> 2, b0 = (tid & 3) * 16;
@@ -253,8 +269,10 @@ __device__ __forceinline__ void brr_gram_tile(const double* __restrict__ Xt, int
   for (int64_t k0 = 0; k0 < n; k0 += BB) {
     for (int e = tid; e < BB * BB; e += 256) {
       const int r = e / BB, c = e % BB;
-      TR[r][c] = (r0 + r < p && k0 + c < n) ? Xt[(r0 + r) * ldx + k0 + c] : 0.0;
-      TC[r][c] = (c0 + r < p && k0 + c < n) ? Xt[(c0 + r) * ldx + k0 + c] : 0.0;
+      bool in = k0 + c < n;
+      if constexpr (SETS) in = in && rows[k0 + c] != 0;
+      TR[r][c] = (r0 + r < p && in) ? Xt[(r0 + r) * ldx + k0 + c] : 0.0;
+      TC[r][c] = (c0 + r < p && in) ? Xt[(c0 + r) * ldx + k0 + c] : 0.0;
     }
     __syncthreads();
     for (int k = 0; k < BB; k++) {
@@ -287,7 +305,8 @@ inline int64_t key_of(const DevBuf& b) { return (int64_t)(uintptr_t)b.p; }  // a
 // Pooled per-device sampler contexts (as fit_ctx.h pools the GBLUP fit contexts): a fit leases one,
 // its buffers only grow, so repeated fits of one shape allocate no device memory after the first
 // (cvmultithread! runs bayesian("BRR") once per fold). BRR and BayesA/B/C fits that alternate on
-// one context keep both captured graphs; the ordinal fits have a third, the multi-chain fits a fourth.
+// one context keep both captured graphs; the ordinal fits have a third, the multi-chain fits a fourth, the
+// multi-chain fits with training sets a fifth.
 struct BrrCtx {
   int dev = 0;
   Stream stream;
@@ -297,13 +316,16 @@ struct BrrCtx {
   DevBuf trace;                            // GBM_BRR_TRACE timestamps of this context's last sweep
   DevBuf dind, dbar, varBj, pk, vpart, bst;  // gbm_bayes_fit: indicators, PIP, varB_j, step constants, partial sums, state
   DevBuf oys, oyh, ocls, opart, oprob, ost;  // gbm_bayes_fit_ordinal: y*, ŷ, classes, min/max partials, P(class), state
+  DevBuf srows, smask, sof, snrows;  // gbm_bayes_fit_multi_rows: the sets' row bytes, the chain-bit words, set_of, n_c
   IterGraph brr_graph, bayes_graph, ordinal_graph, multi_graph;  // multi_graph: gbm_bayes_fit_multi
+  IterGraph rows_graph;                                          // gbm_bayes_fit_multi_rows
   ~BrrCtx() {
     (void)hipSetDevice(dev);
     brr_graph.drop();
     bayes_graph.drop();
     ordinal_graph.drop();
     multi_graph.drop();
+    rows_graph.drop();
   }
 };
 struct BrrLease {
@@ -314,7 +336,8 @@ struct BrrLease {
 };
 
 // The checks gbm_brr_fit and gbm_bayes_fit share (`entry` opens the error text): the arguments, then
-// (after a caller's own checks) the sampling schedule, the phenotypes and the device.
+// (after a caller's own checks) the sampling schedule, the phenotypes (y = nullptr: the caller has checked
+// them) and the device.
 int gibbs_check_args(const char* entry, const double* X, const double* y, const double* b_hat_out, int64_t n, int64_t p,
                      int64_t ldx, int64_t n_iter, int64_t n_burnin, int64_t thin, double r2, double df0);
 int gibbs_check_run(const char* entry, const double* y, int64_t n, int64_t n_iter, int64_t n_burnin, int64_t thin,
@@ -340,6 +363,25 @@ struct GibbsPrior {
   std::vector<double> e0;  // npad values
 };
 int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const GibbsData& g, GibbsPrior& pr);
+// the same over a set of individuals (rows[i] != 0, nc of them, in increasing order; cm and xx the set's column
+// means and Σx²): e0 is 0 at the others and y is not read there. rows = nullptr: all n (nc = n).
+int gibbs_prior_rows(const char* entry, const double* y, int64_t n, int64_t p, int64_t npad, const uint8_t* rows,
+                     int64_t nc, const double* cm, const double* xx, GibbsPrior& pr);
+
+// The training sets of gbm_bayes_fit_multi_rows on the host: nsets rows of n bytes (pitch ldrows), the chains' sets
+// and, filled by the checks and by gibbs_sets, the sets' sizes and their column means and Σx² (nsets x p each).
+struct RowSetsHost {
+  int64_t nsets = 0;
+  const uint8_t* rows = nullptr;
+  int64_t ldrows = 0;
+  const int* set_of = nullptr;
+  std::vector<int64_t> nrows;
+  std::vector<double> cm, xx;
+};
+// Per-set statistics on a context whose genotypes are uploaded: colmean and x2 at s·p, the Gram blocks W at
+// s·nblk·64·64, each over the set's individuals (a held-out one enters as 0.0); the chain-bit words, set_of and
+// n_c of nchains chains for the iteration's kernels. Fills rs.cm and rs.xx; the stream is synchronised.
+int gibbs_sets(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, int64_t nblk, int64_t nchains, RowSetsHost& rs);
 // The tail of a fit: the final state (fin_bytes from `state` into fin) and the posterior means to
 // the host, b_hat_out[0] = *mubar (a field of fin), then the optional y_pred = μ̄ + X b̄. `chain`: which
 // chain of a multi-chain fit (entry `chain` of the state array, the means at chain·p).
@@ -360,14 +402,21 @@ int bayes_setup(const char* entry, BrrCtx& cx, int model, const double* X, int64
 // sized for nchains chains, the genotypes and the Gram blocks (stream synchronised). Per chain: y's prior
 // moments, the start state st0 and the start values of the chain's e, b, d, varB_j and running means
 // (chain c's arrays lie at c times the one-chain size in the context's buffers).
-int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, int64_t nchains, GibbsData& g);
+// rs (gbm_bayes_fit_multi_rows): per-set statistics and Gram blocks (gibbs_sets) in place of the common ones.
+int bayes_setup_shared(BrrCtx& cx, const double* X, int64_t n, int64_t p, int64_t ldx, int64_t nchains, GibbsData& g,
+                       RowSetsHost* rs = nullptr);
 int bayes_start(const char* entry, BrrCtx& cx, int64_t chain, int model, int64_t n, int64_t p, const double* y,
                 int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts, uint64_t seed,
                 const GibbsData& g, BayesState& st0);
+// bayes_start after the prior moments: the start state and start values from pr (e0 of npad values)
+int bayes_start_from(BrrCtx& cx, int64_t chain, int model, int64_t p, int64_t npad, const GibbsPrior& pr,
+                     int64_t n_burnin, int64_t thin, double r2, double df0, double prob_in, double counts,
+                     uint64_t seed, BayesState& st0);
 // steps 1 and 2 of an iteration on the states st[0 .. nchains): the step constants, μ, block 0's partial dots,
-// one chain launch per 64-marker block with per_wg (1 or 4) chains in a workgroup row
+// one chain launch per 64-marker block with per_wg (1 or 4) chains in a workgroup row; rs: the chains' training
+// sets (the SETS instantiations of the kernels)
 void bayes_enqueue_chain(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, BayesState* st, int64_t nchains = 1,
-                         int per_wg = 1);
+                         int per_wg = 1, const RowSets* rs = nullptr);
 // step 3's per-marker variances and the partial sums of the scalar draws (vpart)
 void bayes_enqueue_var(BrrCtx& cx, int64_t n, int64_t p, BayesState* st, int64_t nchains = 1);
 inline int64_t bayes_var_blocks(int64_t n, int64_t p) { return (std::max(n, p) + 255) / 256; }

@@ -29,6 +29,33 @@ __global__ void __launch_bounds__(256) brr_colstats_kernel(const double* __restr
   }
 }
 
+// The same per set of individuals (gbm_bayes_fit_multi_rows): blockIdx.y is the set s, rows[s·ldx + i] != 0 marks
+// its nrows[s] individuals; the others enter as 0.0 in the same order, so a set that is a prefix of the
+// individuals has the bits of brr_colstats_kernel on that prefix. colmean and x2 at s·p.
+__global__ void __launch_bounds__(256) brr_colstats_sets_kernel(const double* __restrict__ Xt, int64_t ldx, int64_t p,
+                                                                int64_t n, const uint8_t* __restrict__ rows,
+                                                                const int64_t* __restrict__ nrows,
+                                                                double* __restrict__ colmean, double* __restrict__ x2) {
+  __shared__ double red[4];
+  const int64_t set = blockIdx.y;
+  rows += set * ldx;
+  for (int64_t j = blockIdx.x; j < p; j += gridDim.x) {
+    const double* row = Xt + j * ldx;
+    double s = 0.0, ss = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+      const double v = rows[i] ? row[i] : 0.0;
+      s += v;
+      ss += v * v;
+    }
+    s = brr_block_sum<256>(s, red);
+    ss = brr_block_sum<256>(ss, red);
+    if (threadIdx.x == 0) {
+      colmean[set * p + j] = s / (double)nrows[set];
+      x2[set * p + j] = ss;
+    }
+  }
+}
+
 // Gram blocks, one 64x64 block per workgroup (brr_gram_tile; row-major; rows/cols past p are
 // zero); one-time setup. nw = 1: W[b] = X_BᵀX_B for the 64-marker
 // blocks B = [64b, 64b + 64). nw = 3 (128-marker launches of the byte path, halves A and B of
@@ -41,6 +68,15 @@ __global__ void __launch_bounds__(256) brr_gram_kernel(const double* __restrict_
   const int64_t r0 = nw == 1 ? blk * BB : blk * 2 * BB + (w >= 1 ? BB : 0);
   const int64_t c0 = nw == 1 ? blk * BB : blk * 2 * BB + (w == 2 ? BB : 0);
   brr_gram_tile(Xt, ldx, p, n, r0, c0, W + (int64_t)blockIdx.x * BB * BB, BB);
+}
+
+// W[s][b] = X_BᵀX_B over the individuals of set s (blockIdx.y; rows as brr_colstats_sets_kernel), at s·wstride
+__global__ void __launch_bounds__(256) brr_gram_sets_kernel(const double* __restrict__ Xt, int64_t ldx, int64_t p,
+                                                            int64_t n, const uint8_t* __restrict__ rows,
+                                                            int64_t wstride, double* __restrict__ W) {
+  const int64_t r0 = (int64_t)blockIdx.x * BB;
+  brr_gram_tile<true>(Xt, ldx, p, n, r0, r0, W + (int64_t)blockIdx.y * wstride + (int64_t)blockIdx.x * BB * BB, BB,
+                      rows + (int64_t)blockIdx.y * ldx);
 }
 
 // partials of block 0 at the start of an iteration (after the intercept update); blockIdx.y is the
@@ -125,7 +161,7 @@ int gibbs_check_run(const char* entry, const double* y, int64_t n, int64_t n_ite
   if (n_iter <= n_burnin || (n_iter / thin) <= (n_burnin / thin))
     return fail(GBM_E_ARG,
                 std::string(entry) + ": no post-burn-in sample (need a multiple of thin in (n_burnin, n_iter])");
-  GBM_TRY(check_y(y, n, n, 1));
+  if (y) GBM_TRY(check_y(y, n, n, 1));
   std::vector<int> devs;
   GBM_TRY(check_devices(&device, 1, devs));
   dev_out = devs[0];
@@ -196,26 +232,73 @@ void gibbs_dots0(BrrCtx& cx, int64_t n, int64_t p, const GibbsData& g, bool byte
                                                             (const double*)cx.e.p, g.npad, (double*)cx.r.p, ldr);
 }
 
+int gibbs_sets(BrrCtx& cx, int64_t n, int64_t p, int64_t npad, int64_t nblk, int64_t nchains, RowSetsHost& rs) {
+  const int dev = cx.dev;
+  hipStream_t s = cx.stream.s;
+  const int64_t S = rs.nsets, wstride = nblk * BB * BB;
+  GBM_TRY(ensure(cx.colmean, dev, S * p * 8));
+  GBM_TRY(ensure(cx.x2, dev, S * p * 8));
+  GBM_TRY(ensure(cx.W, dev, S * wstride * 8));
+  GBM_TRY(ensure(cx.srows, dev, S * npad));
+  GBM_TRY(ensure(cx.smask, dev, npad * 4));
+  GBM_TRY(ensure(cx.sof, dev, nchains * 4));
+  GBM_TRY(ensure(cx.snrows, dev, (nchains + S) * 8));
+  std::vector<uint32_t> mask((size_t)npad, 0u);
+  std::vector<int64_t> nr((size_t)(nchains + S));
+  for (int64_t c = 0; c < nchains; c++) {
+    const uint8_t* r = rs.rows + rs.set_of[c] * rs.ldrows;
+    for (int64_t i = 0; i < n; i++) mask[(size_t)i] |= r[i] ? 1u << c : 0u;
+    nr[(size_t)c] = rs.nrows[(size_t)rs.set_of[c]];
+  }
+  for (int64_t t = 0; t < S; t++) nr[(size_t)(nchains + t)] = rs.nrows[(size_t)t];
+  GBM_HIP_TRY(hipMemsetAsync(cx.srows.p, 0, (size_t)(S * npad), s));
+  GBM_HIP_TRY(hipMemcpy2DAsync(cx.srows.p, npad, rs.rows, rs.ldrows, n, S, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.smask.p, mask.data(), npad * 4, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.sof.p, rs.set_of, nchains * 4, hipMemcpyHostToDevice, s));
+  GBM_HIP_TRY(hipMemcpyAsync(cx.snrows.p, nr.data(), (nchains + S) * 8, hipMemcpyHostToDevice, s));
+  brr_colstats_sets_kernel<<<dim3((unsigned)std::min<int64_t>(p, 4096), (unsigned)S), 256, 0, s>>>(
+      (const double*)cx.Xt.p, npad, p, n, (const uint8_t*)cx.srows.p, (const int64_t*)cx.snrows.p + nchains,
+      (double*)cx.colmean.p, (double*)cx.x2.p);
+  GBM_LAUNCH_CHECK();
+  brr_gram_sets_kernel<<<dim3((unsigned)nblk, (unsigned)S), 256, 0, s>>>(
+      (const double*)cx.Xt.p, npad, p, n, (const uint8_t*)cx.srows.p, wstride, (double*)cx.W.p);
+  GBM_LAUNCH_CHECK();
+  rs.cm.resize((size_t)(S * p));
+  rs.xx.resize((size_t)(S * p));
+  GBM_HIP_TRY(hipMemcpyAsync(rs.cm.data(), cx.colmean.p, S * p * 8, hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipMemcpyAsync(rs.xx.data(), cx.x2.p, S * p * 8, hipMemcpyDeviceToHost, s));
+  GBM_HIP_TRY(hipStreamSynchronize(s));  // mask and nr leave scope
+  return GBM_OK;
+}
+
 int gibbs_prior(const char* entry, const double* y, int64_t n, int64_t p, const GibbsData& g, GibbsPrior& pr) {
+  return gibbs_prior_rows(entry, y, n, p, g.npad, nullptr, n, g.cm.data(), g.xx.data(), pr);
+}
+
+int gibbs_prior_rows(const char* entry, const double* y, int64_t n, int64_t p, int64_t npad, const uint8_t* rows,
+                     int64_t nc, const double* cm, const double* xx, GibbsPrior& pr) {
   // BGLR defaults (setLT.BRR and the residual prior): var(y) with ddof 1
   double ym = 0.0;
-  for (int64_t i = 0; i < n; i++) ym += y[i];
-  ym /= (double)n;
+  for (int64_t i = 0; i < n; i++)
+    if (!rows || rows[i]) ym += y[i];
+  ym /= (double)nc;
   double vy = 0.0;
-  for (int64_t i = 0; i < n; i++) vy += (y[i] - ym) * (y[i] - ym);
-  vy /= (double)(n - 1);
+  for (int64_t i = 0; i < n; i++)
+    if (!rows || rows[i]) vy += (y[i] - ym) * (y[i] - ym);
+  vy /= (double)(nc - 1);
   double msx = 0.0, smsq = 0.0;
   for (int64_t j = 0; j < p; j++) {
-    msx += g.xx[j];
-    smsq += g.cm[j] * g.cm[j];
+    msx += xx[j];
+    smsq += cm[j] * cm[j];
   }
-  msx = msx / (double)n - smsq;
+  msx = msx / (double)nc - smsq;
   if (!(msx > 0.0)) return fail(GBM_E_DATA, std::string(entry) + ": the markers have no variance");
   pr.ym = ym;
   pr.vy = vy;
   pr.msx = msx;
-  pr.e0.assign(g.npad, 0.0);
-  for (int64_t i = 0; i < n; i++) pr.e0[i] = y[i] - ym;
+  pr.e0.assign(npad, 0.0);
+  for (int64_t i = 0; i < n; i++)
+    if (!rows || rows[i]) pr.e0[i] = y[i] - ym;
   return GBM_OK;
 }
 

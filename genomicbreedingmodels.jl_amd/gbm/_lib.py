@@ -49,7 +49,7 @@ EXPORTS = (
     "gbm_dev_whiten_rows", "gbm_session_gwas", "gbm_session_enet_path", "gbm_dev_standardize_grm_syrk",
     "gbm_dev_grm_symmetrize", "gbm_dev_rows_times_sym", "gbm_dev_rows_times_sym_workspace", "gbm_session_pcs",
     "gbm_debug_sym_eig", "gbm_session_pair_scan", "gbm_bayes_fit_ordinal", "gbm_debug_ordinal_math",
-    "gbm_bayes_fit_multi", "gbm_debug_bayes_multi_stats",
+    "gbm_bayes_fit_multi", "gbm_debug_bayes_multi_stats", "gbm_bayes_fit_multi_rows", "gbm_debug_bayes_rows_stats",
 )
 
 GBM_GRM_DEFAULT, GBM_GRM_FP64, GBM_GRM_EXACT, GBM_GRM_AUTO, GBM_GRM_DROPIN = -1, 0, 1, 2, 3
@@ -230,6 +230,11 @@ def _declare(lib):
                                         I64, P, P, I64]
     lib.gbm_debug_bayes_multi_stats.restype = I32
     lib.gbm_debug_bayes_multi_stats.argtypes = [P, P]
+    lib.gbm_bayes_fit_multi_rows.restype = I32
+    lib.gbm_bayes_fit_multi_rows.argtypes = [I64, P, P, I64, I64, I64, P, I64, I64, P, I64, P, I64, I64, I64, P, P, P,
+                                             P, P, I32, P, I64, P, I64, P, P, I64]
+    lib.gbm_debug_bayes_rows_stats.restype = I32
+    lib.gbm_debug_bayes_rows_stats.argtypes = [P, P]
     lib.gbm_debug_oom_retries.restype = I32
     lib.gbm_debug_oom_retries.argtypes = [P, P]
     lib.gbm_session_stats.restype = I32

@@ -112,6 +112,25 @@ def bayes_arrays(model: str, X: np.ndarray, y: np.ndarray, *, n_iter: int = 1500
 MAX_CHAINS = 32  # include/gbm.h GBM_BAYES_MAX_CHAINS
 
 
+def _chain_arguments(models, r2, df0, prob_in, counts, seeds):
+    """The per-chain arrays of a multi-chain call: model codes, priors and seeds (a scalar serves every chain)."""
+    T = len(models)
+
+    def per_chain(v, name, dtype=np.float64):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            return np.full(T, v, dtype=dtype)
+        if a.shape != (T,):
+            raise ArgumentError(f"`{name}` must be a scalar or have one entry per chain ({T}), got shape {a.shape}")
+        return np.ascontiguousarray(a, dtype=dtype)
+
+    mod = np.array([BAYES_MODELS[m] for m in models], dtype=np.intc)
+    r2, df0 = per_chain(r2, "r2"), per_chain(df0, "df0")
+    prob_in, counts = per_chain(prob_in, "prob_in"), per_chain(counts, "counts")
+    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in per_chain(seeds, "seeds", object)], dtype=np.uint64)
+    return mod, r2, df0, prob_in, counts, seeds
+
+
 def bayes_multi_arrays(models, X: np.ndarray, Y: np.ndarray, *, n_iter: int = 1500, n_burnin: int = 500, thin: int = 5,
                        r2=0.5, df0=5.0, prob_in=0.5, counts=10.0, seeds=42, device: int = 0):
     """T = len(models) independent BayesA / BayesB / BayesC chains over one X in one pass (``gbm_bayes_fit_multi``):
@@ -131,19 +150,7 @@ def bayes_multi_arrays(models, X: np.ndarray, Y: np.ndarray, *, n_iter: int = 15
     if Y.ndim != 2 or Y.shape != (n, T):
         raise ArgumentError(f"Y must have one column of {n} phenotypes per chain, ({n}, {T}); got {Y.shape}")
     Y = np.asfortranarray(Y)
-
-    def per_chain(v, name, dtype=np.float64):
-        a = np.asarray(v)
-        if a.ndim == 0:
-            return np.full(T, v, dtype=dtype)
-        if a.shape != (T,):
-            raise ArgumentError(f"`{name}` must be a scalar or have one entry per chain ({T}), got shape {a.shape}")
-        return np.ascontiguousarray(a, dtype=dtype)
-
-    mod = np.array([BAYES_MODELS[m] for m in models], dtype=np.intc)
-    r2, df0 = per_chain(r2, "r2"), per_chain(df0, "df0")
-    prob_in, counts = per_chain(prob_in, "prob_in"), per_chain(counts, "counts")
-    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in per_chain(seeds, "seeds", object)], dtype=np.uint64)
+    mod, r2, df0, prob_in, counts, seeds = _chain_arguments(models, r2, df0, prob_in, counts, seeds)
     b_hat = np.zeros((p + 1, T), order="F")
     y_pred = np.zeros((n, T), order="F")
     var = np.zeros((3, T), order="F")
@@ -154,6 +161,50 @@ def bayes_multi_arrays(models, X: np.ndarray, Y: np.ndarray, *, n_iter: int = 15
                                  _lib.ptr(seeds), int(device), _lib.ptr(b_hat), p + 1, _lib.ptr(y_pred), n,
                                  _lib.ptr(var), _lib.ptr(pip), p)
     _lib.check(rc, "gbm_bayes_fit_multi")
+    return b_hat, y_pred, var, pip
+
+
+def bayes_multi_rows_arrays(models, X: np.ndarray, Y: np.ndarray, sets, set_of, *, n_iter: int = 1500,
+                            n_burnin: int = 500, thin: int = 5, r2=0.5, df0=5.0, prob_in=0.5, counts=10.0, seeds=42,
+                            device: int = 0):
+    """``bayes_multi_arrays`` with a training set per chain (``gbm_bayes_fit_multi_rows``): ``sets`` is an
+    (nsets, n) boolean or uint8 array (1 = a training row) and chain c trains on ``sets[set_of[c]]``; ``Y[i, c]``
+    is read only at the chain's training rows (it may be NaN elsewhere). Returns what ``bayes_multi_arrays``
+    returns, ``y_pred`` over all n rows: at a chain's held-out rows it is the fold's prediction."""
+    models = list(models)
+    for m in models:
+        if m not in BAYES_MODELS:
+            raise ArgumentError(f"model `{m}` is not one of {tuple(BAYES_MODELS)}")
+    T = len(models)
+    if not 1 <= T <= MAX_CHAINS:
+        raise ArgumentError(f"bayes_multi_rows_arrays runs 1 to {MAX_CHAINS} chains per call, got {T}")
+    X = np.asfortranarray(np.asarray(X, dtype=np.float64))
+    Y = np.asarray(Y, dtype=np.float64)
+    n, p = X.shape
+    if Y.ndim != 2 or Y.shape != (n, T):
+        raise ArgumentError(f"Y must have one column of {n} phenotypes per chain, ({n}, {T}); got {Y.shape}")
+    Y = np.asfortranarray(Y)
+    sets = np.asarray(sets)
+    if sets.ndim != 2 or sets.shape[1] != n or sets.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        raise ArgumentError(f"sets must be a boolean or uint8 array of shape (nsets, {n}); got {sets.dtype} "
+                            f"{sets.shape}")
+    sets = np.ascontiguousarray(sets.view(np.uint8) if sets.dtype == bool else sets)
+    set_of = np.asarray(set_of)
+    if set_of.shape != (T,) or not np.issubdtype(set_of.dtype, np.integer):
+        raise ArgumentError(f"set_of must hold one set index per chain ({T}), got shape {set_of.shape}")
+    set_of = np.ascontiguousarray(set_of, dtype=np.intc)
+    mod, r2, df0, prob_in, counts, seeds = _chain_arguments(models, r2, df0, prob_in, counts, seeds)
+    b_hat = np.zeros((p + 1, T), order="F")
+    y_pred = np.zeros((n, T), order="F")
+    var = np.zeros((3, T), order="F")
+    pip = np.zeros((p, T), order="F")
+    lib = _lib.load()
+    rc = lib.gbm_bayes_fit_multi_rows(T, _lib.ptr(mod), _lib.ptr(X), n, p, n, _lib.ptr(Y), n, sets.shape[0],
+                                      _lib.ptr(sets), n, _lib.ptr(set_of), int(n_iter), int(n_burnin), int(thin),
+                                      _lib.ptr(r2), _lib.ptr(df0), _lib.ptr(prob_in), _lib.ptr(counts),
+                                      _lib.ptr(seeds), int(device), _lib.ptr(b_hat), p + 1, _lib.ptr(y_pred), n,
+                                      _lib.ptr(var), _lib.ptr(pip), p)
+    _lib.check(rc, "gbm_bayes_fit_multi_rows")
     return b_hat, y_pred, var, pip
 
 

@@ -140,6 +140,86 @@ def _run_bayes_groups(parts, cvs, genomes, phenomes, errors):
                 errors.append((jb[0], str(e)))
 
 
+def _bayes_fold_groups(jobs, cvs, genomes, phenomes):
+    """``bayes_folds``: the BayesA / BayesB / BayesC jobs (i, model, loci) that share the trait, the loci and the
+    schedule, whatever their training entries (the replications x folds x models of a trait in ``cvbulk``), as lists
+    of at most 32 chains for one ``gbm_bayes_fit_multi_rows`` call each.
+    A chain's set is its job's training rows with a finite phenotype of its trait, as a boolean mask over
+    ``genomes.entries``; chains with identical sets share one. Returns (parts, the jobs that share with no
+    other); a part is (chains, sets, set_of, loci, n_iter, n_burnin) with chains (i, name, trait, rows): rows the
+    job's training rows in the caller's order after the missing-phenotype drop. The chains of one set stay in one
+    part (a set of more than 32 chains fills parts of its own)."""
+    Yall = np.asarray(phenomes.phenotypes, dtype=np.float64)
+    pos_entry = {e: k for k, e in enumerate(genomes.entries)}
+    n_all = len(genomes.entries)
+    groups = {}
+    for i, model, loci in jobs:
+        cv = cvs[i]
+        name, n_iter, n_burnin = _bayes_chain(model)
+        rows = np.array([pos_entry[e] for e in cv.fit.entries], dtype=np.int64)
+        trait = phenomes.traits.index(cv.fit.trait)
+        rows = rows[np.isfinite(Yall[rows, trait])]
+        mask = np.zeros(n_all, dtype=bool)
+        mask[rows] = True
+        key = (trait, np.asarray(loci, dtype=np.int64).tobytes(), n_iter, n_burnin)
+        by_set = groups.setdefault(key, (loci, {}, [model]))[1]
+        by_set.setdefault(mask.tobytes(), (mask, []))[1].append((i, name, trait, rows))
+    parts, single = [], []
+    for (_, _, n_iter, n_burnin), (loci, by_set, first_model) in groups.items():
+        if sum(len(chains) for _, chains in by_set.values()) == 1:  # nothing to share: the one-model path
+            (_, chains), = by_set.values()
+            single.append((chains[0][0], first_model[0], loci))
+            continue
+        open_part = None
+        for mask, chains in by_set.values():
+            for c0 in range(0, len(chains), bayes.MAX_CHAINS):
+                piece = chains[c0:c0 + bayes.MAX_CHAINS]
+                if open_part is None or len(open_part[0]) + len(piece) > bayes.MAX_CHAINS:
+                    open_part = ([], [], [], loci, n_iter, n_burnin)
+                    parts.append(open_part)
+                open_part[0].extend(piece)
+                open_part[2].extend([len(open_part[1])] * len(piece))
+                open_part[1].append(mask)
+    return parts, single
+
+
+def _run_bayes_fold_groups(parts, cvs, genomes, phenomes, errors):
+    """Each part of _bayes_fold_groups as one fit over all entries (``bayes.bayes_multi_rows_arrays``): X is
+    ``allele_frequencies[:, loci]``, chain c's phenotypes its trait's column. Each job's Fit is assembled as on the
+    one-model path (entries and populations in the caller's order, ``y_pred`` the call's column at those rows,
+    metrics from that) and validated as there; an error of the fit is recorded for each of its jobs."""
+    Yall = np.asarray(phenomes.phenotypes, dtype=np.float64)
+    G = np.asarray(genomes.allele_frequencies, dtype=np.float64)
+    for chains, sets, set_of, loci, n_iter, n_burnin in parts:
+        try:
+            b_hat, y_pred, _, _ = bayes.bayes_multi_rows_arrays(
+                [ch[1] for ch in chains], G[:, loci], Yall[:, [ch[2] for ch in chains]], np.array(sets), set_of,
+                n_iter=n_iter, n_burnin=n_burnin)
+        except (GBMError, ArgumentError) as e:
+            errors.extend((ch[0], str(e)) for ch in chains)
+            continue
+        for c, (i, name, trait, rows) in enumerate(chains):
+            cv = cvs[i]
+            try:
+                fit = Fit(n=rows.size, l=len(loci) + 1)
+                fit.model = name.lower()
+                fit.b_hat_labels = ["intercept"] + [genomes.loci_alleles[k] for k in loci]
+                fit.trait = phenomes.traits[trait]
+                fit.entries = [genomes.entries[r] for r in rows]
+                fit.populations = [genomes.populations[r] for r in rows]
+                fit.y_true = Yall[rows, trait].copy()
+                fit.b_hat = np.ascontiguousarray(b_hat[:, c])
+                fit.y_pred = np.ascontiguousarray(y_pred[rows, c])
+                fit.metrics = metrics(fit.y_true, fit.y_pred)
+                if not fit.checkdims():
+                    raise GBMError("Error fitting " + fit.model + ".")
+                cvs[i] = validate(fit, genomes, phenomes,
+                                  idx_validation=[genomes.entries.index(e) + 1 for e in cv.validation_entries],
+                                  replication=cv.replication, fold=cv.fold)
+            except (GBMError, ArgumentError) as e:
+                errors.append((i, str(e)))
+
+
 def _model_label(model) -> str:
     if isinstance(model, functools.partial):
         return model.keywords.get("model_label", "gblup") if model.func is gblup else str(model.func.__name__)
@@ -230,13 +310,17 @@ def _run_device_jobs(session: GenotypeSession, jobs, cvs, genomes, phenomes, err
 
 
 def cvmultithread(cvs, *, genomes: Genomes, phenomes: Phenomes, models_vector, verbose: bool = False,
-                  devices=None):
+                  devices=None, bayes_folds: bool = False):
     """Mirror of ``cvmultithread!`` (src/cross_validation.jl:151-207). GBLUP jobs run on one
     genotype session per device (one host thread each), grouped by training set so that the
     GRM is built once per set and traits sharing a set are solved together; ``bayesa`` / ``bayesb`` /
     ``bayesc`` jobs that share a training set, loci and schedule run as chains of one multi-chain fit
     (``gbm_bayes_fit_multi``, 32 per pass; the CVs are those of the one-model path, bit for bit); other
-    model callables run as in the reference (called with the six keywords, then ``validate``)."""
+    model callables run as in the reference (called with the six keywords, then ``validate``).
+    ``bayes_folds=True`` groups the ``bayesa`` / ``bayesb`` / ``bayesc`` jobs that share the trait, the loci and the
+    schedule whatever their training entries: the folds of a replication run as chains of one pass over all entries, each on
+    its own training rows (``gbm_bayes_fit_multi_rows``). A fold's sums then run over all entries with exact zeros at
+    the held-out ones, so its CV agrees with the one-model path to rounding (about 1e-12), not bit for bit."""
     if devices is None:
         devices = list(range(max(1, _lib.device_count())))
     pos_loci = {lab: k for k, lab in enumerate(genomes.loci_alleles)}
@@ -282,8 +366,12 @@ def cvmultithread(cvs, *, genomes: Genomes, phenomes: Phenomes, models_vector, v
             for s in sessions:
                 s.close()
     if bayes_jobs:
-        parts, single = _bayes_groups(bayes_jobs, cvs, genomes, phenomes)
-        _run_bayes_groups(parts, cvs, genomes, phenomes, errors)
+        if bayes_folds:
+            parts, single = _bayes_fold_groups(bayes_jobs, cvs, genomes, phenomes)
+            _run_bayes_fold_groups(parts, cvs, genomes, phenomes, errors)
+        else:
+            parts, single = _bayes_groups(bayes_jobs, cvs, genomes, phenomes)
+            _run_bayes_groups(parts, cvs, genomes, phenomes, errors)
         other = sorted(other + single, key=lambda jb: jb[0])
     for i, model, loci in other:
         cv = cvs[i]
@@ -370,14 +458,14 @@ def cvbulk_setup(*, genomes: Genomes, phenomes: Phenomes, models=(gblup,), n_rep
 
 
 def cvbulk(*, genomes: Genomes, phenomes: Phenomes, models=(gblup,), n_replications: int = 5, n_folds: int = 5,
-           seed: int = 42, verbose: bool = False, devices=None):
+           seed: int = 42, verbose: bool = False, devices=None, bayes_folds: bool = False):
     """Mirror of ``cvbulk`` (src/cross_validation.jl:268-401): replicated k-fold CV across all
-    traits and entries. Returns (cvs, notes)."""
+    traits and entries. Returns (cvs, notes). ``bayes_folds``: see ``cvmultithread``."""
     cvs, notes, models_vector = cvbulk_setup(genomes=genomes, phenomes=phenomes, models=models,
                                              n_replications=n_replications, n_folds=n_folds, seed=seed)
     if verbose:
         print("Setup", len(cvs), "cross-validation job/s.")
         print("Skipping", len(notes), "cross-validation job/s.")
     cvmultithread(cvs, genomes=genomes, phenomes=phenomes, models_vector=models_vector, verbose=verbose,
-                  devices=devices)
+                  devices=devices, bayes_folds=bayes_folds)
     return cvs, notes

@@ -756,8 +756,8 @@ int gbm_bayes_fit(int model, const double* X, int64_t n, int64_t p, int64_t ldx,
  * GBM_E_ARG, before any device work: nchains outside [1, 32]; a NULL among models, X, Y, r2, df0,
  * prob_in, counts, seeds, b_hat_out; ldy < n, ldb < p + 1, ldp < n, ldpip < p (of the outputs given);
  * gbm_bayes_fit's checks for every chain, with "chain c" (0-based) in the error text.
- * Not offered: the ordinal response, BRR, more than 32 chains per call, chains on different
- * individuals or markers, chain traces.
+ * Not offered: the ordinal response, BRR, more than 32 chains per call, chains on different markers,
+ * chain traces. Chains on different individuals: gbm_bayes_fit_multi_rows.
  */
 #define GBM_BAYES_MAX_CHAINS 32
 int gbm_bayes_fit_multi(int64_t nchains, const int* models, const double* X, int64_t n, int64_t p, int64_t ldx,
@@ -768,6 +768,39 @@ int gbm_bayes_fit_multi(int64_t nchains, const int* models, const double* X, int
                         double* y_pred_out, int64_t ldp /* n x nchains, may be NULL */,
                         double* var_out /* 3 x nchains, may be NULL */,
                         double* pip_out, int64_t ldpip /* p x nchains, may be NULL */);
+
+/*
+ * ---- Several chains over one genotype matrix, each on its own rows (the folds of a cross-validation) ----
+ * gbm_bayes_fit_multi with a training set per chain: rows holds nsets sets as n bytes each (pitch ldrows; 1 = a
+ * training row, 0 = held out) and chain c trains on the set set_of[c]. Chain c is the sampler of gbm_bayes_fit on
+ * the rows S_c = {i : rows[set_of[c] ldrows + i] = 1} taken in increasing order, with the phenotypes Y[S_c, c]:
+ * every quantity of gbm_bayes_fit's text that sums over individuals runs over S_c with n_c = |S_c| in place of n
+ * (vy, x2_j, MSx, μ's mean and variance, x_jᵀe, Σe², the degrees of freedom df0 + n_c). The random streams are
+ * unchanged: they are indexed by marker and iteration, never by individual. Y at rows outside S_c is never read
+ * as a number and may be NaN. X is uploaded and quantised once and every launch of an iteration serves all
+ * chains; column statistics and Gram blocks are built once per set, so the models of a fold that name one set
+ * share them. (Additive: GBM_VERSION stays 212.)
+ *
+ * y_pred_out[c ldp + i] = b0 + X[i,:] b for all n rows: at the rows outside S_c it is the fold's prediction.
+ * b_hat_out, var_out and pip_out as gbm_bayes_fit_multi. With one set of all rows every output has the bits of
+ * gbm_bayes_fit_multi; with a set that holds the first n_c rows, b_hat_out, var_out and pip_out have the bits of
+ * gbm_bayes_fit on those rows (held-out rows add exact zeros to sums of a fixed order).
+ * GBM_E_ARG, before any device work, with "chain c" or "set s" (0-based) in the text: gbm_bayes_fit_multi's own
+ * refusals (gbm_bayes_fit's checks on each chain's rows); nsets outside [1, nchains]; a NULL rows or set_of;
+ * ldrows < n; a set_of entry outside [0, nsets); a set with fewer than 3 rows or with a byte other than 0 or 1; a
+ * non-finite Y inside a chain's set. GBM_E_DATA naming the set: its markers have no variance on its rows
+ * (MSx <= 0).
+ * Not offered: the ordinal response, BRR, more than 32 chains per call, chains on different markers, chain
+ * traces.
+ */
+int gbm_bayes_fit_multi_rows(int64_t nchains, const int* models, const double* X, int64_t n, int64_t p, int64_t ldx,
+                             const double* Y, int64_t ldy,
+                             int64_t nsets, const uint8_t* rows /* nsets x n, pitch ldrows >= n; 1 = training row */,
+                             int64_t ldrows, const int* set_of /* nchains, each in [0, nsets) */,
+                             int64_t n_iter, int64_t n_burnin, int64_t thin, const double* r2, const double* df0,
+                             const double* prob_in, const double* counts, const uint64_t* seeds, int device,
+                             double* b_hat_out, int64_t ldb, double* y_pred_out, int64_t ldp,
+                             double* var_out, double* pip_out, int64_t ldpip);
 
 /*
  * ---- BayesA, BayesB and BayesC with an ordinal response (threshold model) -------------------
@@ -825,6 +858,8 @@ int gbm_bayes_fit_ordinal(int model, const double* X, int64_t n, int64_t p, int6
 int gbm_debug_brr_stats(int* last_path, int64_t* fallbacks);
 /* How many gbm_bayes_fit_multi calls have completed since load and how many chains they ran. */
 int gbm_debug_bayes_multi_stats(int64_t* calls, int64_t* chains);
+/* The same for gbm_bayes_fit_multi_rows (its calls are not counted above). */
+int gbm_debug_bayes_rows_stats(int64_t* calls, int64_t* chains);
 /* Chunk shape of the last super-block sweep: C workgroups, the first O own R rows of every
  * super-block and take Ko individuals each, the others Kn. */
 int gbm_debug_brr_shape(int* C, int* O, int* R, int* Ko, int* Kn);

@@ -7,8 +7,11 @@ same phenotype cut into K = 4 classes at its quartiles (``--response gaussian,or
 the ratio of the two slopes is the ordinal steps' overhead). ``--chains 1,4,8,24,32`` times gbm_bayes_fit_multi
 with that many chains instead (the models of ``--models`` in turn, one phenotype column and seed per chain) and
 adds the ms per chain-iteration; ``--multi-wg 1`` / ``--multi-wg 4`` force one / four chains per workgroup row
-(GBM_BAYES_MULTI_WG) for the comparison of the two mappings. ``--repeats R`` repeats every measurement (the
-run-to-run spread). Prints one JSON line per measurement."""
+(GBM_BAYES_MULTI_WG) for the comparison of the two mappings. ``--folds F`` times a cross-validation's F folds
+(fold of individual i: i mod F) x the models of ``--models`` two ways: F gbm_bayes_fit_multi calls, one per fold on
+its training rows, and one gbm_bayes_fit_multi_rows call over all rows with a training set per fold; it reports
+the per-iteration slope and the setup (the short fit's time less its iterations) of each. ``--repeats R`` repeats
+every measurement (the run-to-run spread). Prints one JSON line per measurement."""
 import argparse
 import json
 import os
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--chains", default="", help="chain counts of gbm_bayes_fit_multi (comma-separated); empty: none")
     ap.add_argument("--multi-wg", type=int, default=0, choices=(0, 1, 4),
                     help="chains per workgroup row of a multi fit (0: the library's choice)")
+    ap.add_argument("--folds", type=int, default=0, help="folds of the cross-validation comparison; 0: none")
     ap.add_argument("--repeats", type=int, default=1)
     args = ap.parse_args()
     import gbm
@@ -55,6 +59,9 @@ def main():
     _lib.debug_set("GBM_BRR_SWEEP", "0")  # BRR: one launch per block, the schedule the chain launches compare with
     for storage in args.storages.split(","):
         _lib.debug_set("GBM_BRR_I8", None if storage == "bytes" else "0")
+        if args.folds:
+            fold_rows(gbm, _lib, args, X, y, storage, lo, hi)
+            continue
         if chains:
             multi_rows(gbm, _lib, args, chains, X, Y, storage, lo, hi)
             continue
@@ -100,6 +107,57 @@ def multi_rows(gbm, _lib, args, chains, X, Y, storage, lo, hi):
                               "ms_per_chain_iter": ms / T, "block_launches_per_iter": launches,
                               "us_per_block_launch": ms * 1e3 / launches,
                               "cor": float(np.corrcoef(out[1][:, 0], Yt[:, 0])[0, 1])}), flush=True)
+
+
+def fold_rows(gbm, _lib, args, X, y, storage, lo, hi):
+    """F folds x the models: a gbm_bayes_fit_multi call per fold on its training rows against one
+    gbm_bayes_fit_multi_rows call on all rows. The folds' predictions of the two paths are compared."""
+    names = [m for m in args.models.split(",") if m != "BRR"]
+    F, M = args.folds, len(names)
+    fold = np.arange(args.n) % F
+    seeds = [42 + c for c in range(M)]
+    row = {"folds": F, "models": names, "storage": storage, "n": args.n, "p": args.p, "iters": [lo, hi]}
+
+    def slope(fit):
+        ms, s_lo, s_hi, out = per_iteration(fit, lo, hi)
+        return {"seconds": [s_lo, s_hi], "ms_per_iter": ms, "setup_seconds": s_lo - ms * 1e-3 * lo,
+                "ms_per_fold_model_iter": ms / (F * M)}, out
+
+    # one multi call per fold on X[train] (gathering the rows is the caller's cost today and is timed apart)
+    t0 = time.perf_counter()
+    parts = [(np.asfortranarray(X[fold != f]), np.asfortranarray(np.tile(y[fold != f, None], (1, M)))) for f in range(F)]
+    gather = time.perf_counter() - t0
+    _lib.debug_set("GBM_BAYES_MULTI_WG", None)
+
+    def per_fold(it):
+        return [gbm.bayes_multi_arrays(names, Xf, Yf, n_iter=it, n_burnin=it // 2, thin=1, seeds=seeds)
+                for Xf, Yf in parts]
+
+    per_fold(2)  # warm-up: the pooled context's buffers
+    held = None
+    for rep in range(args.repeats):
+        fig, outs = slope(per_fold)
+        held = [outs[f][0] for f in range(F)]  # b_hat per fold
+        print(json.dumps(dict(row, bench="CV folds, a multi fit per fold", calls=F, chains_per_call=M,
+                              gather_seconds=gather, **fig)), flush=True)
+    del parts
+    sets = np.stack([fold != f for f in range(F)])
+    set_of = [f for f in range(F) for _ in range(M)]
+    Yr = np.asfortranarray(np.tile(y[:, None], (1, F * M)))
+    for wg in ((1, 4) if not args.multi_wg else (args.multi_wg,)):
+        _lib.debug_set("GBM_BAYES_MULTI_WG", str(wg))
+        fit = lambda it: gbm.bayes_multi_rows_arrays(names * F, X, Yr, sets, set_of, n_iter=it, n_burnin=it // 2,
+                                                     thin=1, seeds=seeds * F)
+        fit(2)
+        for rep in range(args.repeats):
+            fig, out = slope(fit)
+            worst = max(float(np.abs(out[0][:, f * M + m] - held[f][:, m]).max() / np.abs(held[f][:, m]).max())
+                        for f in range(F) for m in range(M))
+            cor = float(np.corrcoef(out[1][fold == 0, 0], y[fold == 0])[0, 1])
+            print(json.dumps(dict(row, bench="CV folds, one rows fit", calls=1, chains_per_call=F * M,
+                                  chains_per_workgroup=wg, b_hat_rel_diff_from_per_fold=worst,
+                                  held_out_cor_fold0=cor, **fig)), flush=True)
+    _lib.debug_set("GBM_BAYES_MULTI_WG", None)
 
 
 if __name__ == "__main__":
